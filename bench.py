@@ -12,7 +12,8 @@ to rank 0 in one ncclSend/ncclRecv group.  --in-process drives N devices from
 one process (rt_render_opts.devices).  Scaling is strong: the frame is fixed,
 ranks split it.  value = traced samples of all steps / max-over-ranks time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--no-cpu-baseline] [--no-host-rate]
   python bench.py --workload c4        # BASELINE configs[3]: 1M-triangle OBJ, 1920x1080, 256 spp
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
@@ -24,6 +25,13 @@ per GPU, the library's RCCL communicator gathering to rank 0; with --gpus N >
 through rt_render_opts.devices -- ncclCommInitAll communicators and one
 ncclSend / ncclRecv group onto device 0.  The line names the gather the
 library used (rt_render_gather_mode) and its device time.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what takes runs of its own after the timed steps: the host-buffer
+(PCIe-inclusive) frame and the CPU baseline (--no-host-rate and
+--no-cpu-baseline leave one of them out again).  --dump-outputs DIR writes
+the last timed step's linear framebuffer, the array a caller of
+rt_render_device receives, as DIR/frame.npy (float32).
 """
 import argparse
 import ctypes
@@ -386,6 +394,32 @@ def load_profile_field(name, field):
         return None, None
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_rows(height, row_bytes, max_bytes=DUMP_MAX_BYTES):
+    """The rows of a frame --dump-outputs keeps: all of them when the frame
+    fits in max_bytes, else a fixed, seeded sample of whole rows in ascending
+    order (the same rows for every run of the same frame size)."""
+    keep = max(1, max_bytes // row_bytes)
+    if keep >= height:
+        return None
+    import numpy as np
+    return np.sort(np.random.default_rng(2025).choice(height, size=keep, replace=False))
+
+
+def dump_outputs(path, frame):
+    """Write the (H, W, 3) linear f32 framebuffer of the last timed step as
+    <path>/frame.npy (C5's 3840x2160 frame: a row sample, see dump_rows)."""
+    import numpy as np
+    a = frame.contiguous().cpu().numpy().astype(np.float32, copy=False)
+    rows = dump_rows(a.shape[0], a.shape[1] * a.shape[2] * 4)
+    if rows is not None:
+        a = a[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -396,8 +430,13 @@ def main():
                     help="c2 = BASELINE configs[1] (the headline metric); c3 / c4 / c5 = configs[2] / [3] / [4]")
     ap.add_argument("--spp", type=int, default=None, help="default: the config's spp")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-rate", action="store_true", help="skip the host-buffer (PCIe-inclusive) frame")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the host-buffer (PCIe-inclusive) frame and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's linear framebuffer as DIR/frame.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-rate", action="store_true",
+                    help="with --full: skip the host-buffer (PCIe-inclusive) frame")
     ap.add_argument("--reference-bvh", action="store_true",
                     help="A/B only: keep the reference BVH topology instead of the SAH rebuild")
     ap.add_argument("--backend", default="nccl",
@@ -415,6 +454,8 @@ def main():
     ap.add_argument("--cpu-row-stride", type=int, default=2)
     ap.add_argument("--cpu-spp", type=int, default=None, help="default: 64 (c2), 36 (c4) -> ~10 s of oracle work")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.spp is None:
         args.spp = WORKLOADS[args.workload][1]
     if args.width is None:
@@ -537,6 +578,8 @@ def main():
     value = frame_samples * args.steps / elapsed / 1e6
     if rank == 0:
         assert torch.isfinite(frame).all().item()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame[:H])
         wc_path = os.path.join(ROOT, "bench_data", f"work_counts_{args.workload}.json")
         wc = json.load(open(wc_path))
         # one launch of the path kernel processes this rank's (or device's) rows
@@ -622,7 +665,7 @@ def main():
         if args.frame_hash:
             import hashlib
             line["frame_sha256"] = hashlib.sha256(frame[:H].contiguous().cpu().numpy().tobytes()).hexdigest()
-        if world_size == 1 and not in_process and not args.no_host_rate:
+        if args.full and world_size == 1 and not in_process and not args.no_host_rate:
             # the PCIe-inclusive rate: rt_render into caller-owned host buffers
             # (linear f32 + sRGB bytes), SURVEY §8(d)'s t_render
             hopts, _hk = rt.Camera._opts(api, args.seed, 0, 1, 0, 1 if args.reference_bvh else 0)
@@ -639,7 +682,7 @@ def main():
                                       "ms": round(dh * 1e3, 3), "kernel_ms": round(hst.kernel_ms, 3),
                                       "note": "one rt_render into host buffers (linear f32 + sRGB u8, PCIe copy "
                                               "included), after the timed steps; not `value`"}
-        if world_size == 1 and not in_process and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not in_process and not args.no_cpu_baseline:
             cpu_spp = args.cpu_spp or {"c2": 64, "c3": 400, "c4": 36, "c5": 16}[args.workload]
             threads, info = usable_cpus()
             if args.cpu_threads:

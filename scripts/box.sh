@@ -4,7 +4,7 @@
 # Steps (STEPS, run in order):
 #   tests       the GPU suite (TESTS, default "tests -m gpu")
 #   checktests  the same on the bounds-checked build (librt_mi355x_check.so)
-#   bench       bench.py BENCH_ARGS for each workload in BENCH_WORKLOADS (default c2)
+#   bench       bench.py --full BENCH_ARGS for each workload in BENCH_WORKLOADS (default c2)
 #   ab          interleaved A/B (scripts/ab.py AB_SPP AB_REPS AB_VARIANTS) on each of AB_WORKLOADS
 #   diag        diagnostic builds, one per "workload:lib:spp" in DIAG_RUNS (scripts/diag.py)
 #   ffp         whole-frame parity (scripts/full_frame_parity.py) for each of FFP (C5 at FFP_C5_SPP)
@@ -29,7 +29,7 @@ for step in ${STEPS:-tests}; do
       rc=$?; tail -3 $O/pytest_check.log; [ $rc -eq 0 ] || { tail -40 $O/pytest_check.log; stop checktests $rc; } ;;
     bench)
       for w in ${BENCH_WORKLOADS:-c2}; do
-        timeout -k 10 ${BENCH_TIMEOUT:-600} python3 bench.py --workload $w ${BENCH_ARGS:-} > $O/bench_$w.json 2> $O/bench_$w.err
+        timeout -k 10 ${BENCH_TIMEOUT:-600} python3 bench.py --full --workload $w ${BENCH_ARGS:-} > $O/bench_$w.json 2> $O/bench_$w.err
         rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench_$w.err; stop "bench $w" $rc; }
         python3 -c "import json; d=json.load(open('$O/bench_$w.json')); r=d['roofline']; cb=d.get('cpu_baseline') or {}; print('bench $w', d['value'], d['ms_per_step'], r['kernel_ms_avg'], r['frac'], cb.get('speedup_whole_host'))"
       done ;;

@@ -31,7 +31,7 @@ for w in ${PROFILE_WORKLOADS:-c2 c3 c4}; do
     c4) BL="--steps 2 --warmup 1"; P="--steps 2 --warmup 1";;
     c5) BL="--steps 1 --warmup 0"; P="--steps 1 --warmup 0 --spp ${C5_PROF_SPP:-256}";;
   esac
-  if [ "${BENCH_LINES:-1}" = 1 ]; then run bench_$w 900 python3 bench.py --workload $w $BL; fi
+  if [ "${BENCH_LINES:-1}" = 1 ]; then run bench_$w 900 python3 bench.py --full --workload $w $BL; fi
   B="bench.py --workload $w $P --no-cpu-baseline --no-host-rate"
   run trace_$w 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$w -o run -- python3 $B
   if [ "${PMC:-1}" = 1 ]; then

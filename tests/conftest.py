@@ -96,6 +96,23 @@ def rccl_standin(tmp_path_factory):
     return so, counts
 
 
+_LIBC = ctypes.CDLL(None, use_errno=True)
+ADDR_NO_RANDOMIZE = 0x0040000  # <sys/personality.h>
+
+
+def no_aslr():
+    """preexec_fn of a sanitized test program: address-space randomisation off
+    for that child alone (personality(2), what `setarch -R` does).  Under a
+    kernel with 32 bits of mmap randomisation (vm.mmap_rnd_bits) a mapping can
+    land outside the ranges the sanitizer runtimes of gcc 11 lay their shadow
+    over, and the program ends before main with "FATAL: ThreadSanitizer:
+    unexpected memory mapping".  Where the call is not allowed the child runs
+    as it is."""
+    cur = _LIBC.personality(0xffffffff)
+    if cur != -1:
+        _LIBC.personality(cur | ADDR_NO_RANDOMIZE)
+
+
 def rmse_per_channel(a, b):
     import numpy as np
 

@@ -19,6 +19,7 @@
 // failure.  Mode "planted" reads a device output before rt_render_device_wait
 // -- a race TSan must report (the harness's proof that it can).
 // Usage: launcher_tsan <fake_rccl.so> [planted]; prints "ok <frames>".
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -148,6 +149,13 @@ int main(int argc, char** argv) {
         rt_render_opts o;
         rt_render_opts_default(&o);
         CHECK(rt_render_device(w.s, w.world, -1, &w.cam, &o, out) == 0);
+        // wait a third of the stub kernel's sleep (no lock taken): the stream's
+        // thread has then taken the kernel off its queue.  A thread that wakes
+        // late and takes it only after this one is inside
+        // rt_render_device_wait has locked the queue after the read below,
+        // which orders the read before the kernel's write and hides the race
+        const char* delay = std::getenv("HIP_STUB_DELAY_US");
+        std::this_thread::sleep_for(std::chrono::microseconds(delay ? std::atol(delay) / 3 : 0));
         volatile float v = out[0];  // the planted race
         (void)v;
         CHECK(rt_render_device_wait(w.s, nullptr) == 0);

@@ -1,6 +1,8 @@
 """bench.py's output contract on the GPU: one JSON line with the driver's
-keys, the roofline and cpu_baseline objects, consistent arithmetic (value =
-frame samples x steps / wall time), at a small size so it runs in seconds."""
+keys, the roofline and (with --full) cpu_baseline objects, consistent
+arithmetic (value = frame samples x steps / wall time), at a small size so it
+runs in seconds; a plain run measures the timed steps alone and can dump the
+last step's frame."""
 import json
 import os
 import subprocess
@@ -23,7 +25,7 @@ def run_bench(*args):
 
 
 def test_bench_line_contract():
-    d = run_bench("--steps", "2", "--warmup", "1", "--width", "256", "--spp", "16", "--cpu-spp", "1",
+    d = run_bench("--full", "--steps", "2", "--warmup", "1", "--width", "256", "--spp", "16", "--cpu-spp", "1",
                   "--cpu-row-stride", "16")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -55,6 +57,29 @@ def test_bench_line_contract():
         whole = cb["whole_host_estimated"]
         assert whole["value"] > 0 and "ESTIMATED" in whole["basis"]
         assert abs(cb["speedup_whole_host"] - d["value"] / whole["value"]) <= 0.01 * cb["speedup_whole_host"] + 0.01
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) measures nothing beside the timed steps -- no
+    cpu_baseline, no host_inclusive -- keeps the driver's keys, runs exactly
+    --steps timed steps, and --dump-outputs writes the last step's linear
+    framebuffer: float32, (H, W, 3), the bytes the line's frame hash covers."""
+    import hashlib
+
+    import numpy as np
+    out = tmp_path / "dump"
+    d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "256", "--spp", "16", "--frame-hash",
+                  "--dump-outputs", str(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert "cpu_baseline" not in d and "host_inclusive" not in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    samples = 256 * 144 * 16
+    assert abs(d["value"] - samples / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"] + 1e-3
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    a = np.load(out / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (144, 256, 3) and np.isfinite(a).all() and a.mean() > 0.05
+    assert hashlib.sha256(a.tobytes()).hexdigest() == d["frame_sha256"]
 
 
 def test_bench_two_ranks_gloo():

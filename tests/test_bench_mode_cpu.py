@@ -41,6 +41,32 @@ def test_device_list(bench):
         bench.parse_devices("0,5", 2, 4)
 
 
+def test_dump_rows_sample(bench):
+    """--dump-outputs keeps a whole frame that fits in 64 MB and a fixed,
+    seeded, ascending row sample of a larger one (C5: 3840 x 2160 x 3 f32)."""
+    assert bench.dump_rows(1080, 1920 * 3 * 4) is None  # C2: 24.9 MB
+    row = 3840 * 3 * 4
+    rows = bench.dump_rows(2160, row)
+    assert len(rows) == 64 * 1000 * 1000 // row and len(rows) * row <= 64 * 1000 * 1000
+    assert len(set(rows.tolist())) == len(rows) and rows.min() >= 0 and rows.max() < 2160
+    assert (rows[1:] > rows[:-1]).all()
+    assert (bench.dump_rows(2160, row) == rows).all()  # the same rows every run
+    assert bench.dump_rows(10, 100, max_bytes=250).tolist() == bench.dump_rows(10, 100, max_bytes=299).tolist()
+    assert len(bench.dump_rows(10, 100, max_bytes=50)) == 1  # never empty
+
+
+def test_dump_outputs_file(bench, tmp_path):
+    import numpy as np
+    import torch
+    frame = torch.arange(5 * 7 * 3, dtype=torch.float32).reshape(5, 7, 3)
+    d = tmp_path / "new" / "dir"
+    bench.dump_outputs(str(d), frame)
+    assert sorted(os.listdir(d)) == ["frame.npy"]
+    a = np.load(d / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (5, 7, 3)
+    assert (a == frame.numpy()).all()
+
+
 def test_gather_mode_names_match_header(bench):
     text = open(os.path.join(ROOT, "include", "rt_mi355x.h")).read()
     for code, name in ((0, "NONE"), (1, "RCCL_COMM"), (2, "RCCL_DEVICES"), (3, "PEER_COPY")):

@@ -26,7 +26,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, no_aslr
 
 PKG_DIR = os.path.join(ROOT, "raytracer-2025_amd")
 EXE = os.path.join(PKG_DIR, "_obj", "san", "launcher_tsan")
@@ -43,7 +43,8 @@ def built():
 def _run(delay_us, *extra):
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66", HIP_STUB_DELAY_US=str(delay_us))
     env.pop("RT_RCCL_LIB", None)
-    return subprocess.run([EXE, RCCL, *extra], capture_output=True, text=True, timeout=300, env=env)
+    return subprocess.run([EXE, RCCL, *extra], capture_output=True, text=True, timeout=300, env=env,
+                          preexec_fn=no_aslr)
 
 
 @pytest.mark.parametrize("delay_us", [0, 300, 3000])

@@ -226,16 +226,15 @@ def test_terrain_loads_on_both(product, oracle, rt, capi, scenes, tmp_path):
     assert st.panics == 0 and np.isfinite(lin).all() and lin.mean() > 0.05
 
 
-REF_ASSETS = "/root/reference/assets/Final"
+REF_ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_assets")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference assets not present (GPU box)")
 @pytest.mark.parametrize("name,tier", [("镜子.obj", 2), ("水面.obj", 2)])
 def test_reference_vanilla_assets_load(product, oracle, rt, capi, name, tier):
     """The two OBJs the reference's obj_scene loads with vanilla_material = true
     (main.rs:213, 217): the mirror (Pm 1 -> Metal, Ke 0 0 0 -> DiffuseLight
     around it) and the water (Tf 1 -> Dielectric, map_Bump "-bm 1 file" whose
-    file is absent -> cyan normal map).  Read in place, not copied."""
+    file is absent -> cyan normal map).  Copies under tests/golden/ref_assets."""
     path = os.path.join(REF_ASSETS, name)
     s, w = load(product, rt, path)
     info = prims(product, capi, s, w)
@@ -300,12 +299,11 @@ def test_obj_image_maps_load(product, oracle, rt, capi, tmp_path, names, tier):
 
 
 def test_reference_mc_obj_needs_disney(product, oracle, rt, capi):
-    """The reference's own assets/Final/mc.obj (read in place) decodes its PNG
+    """The reference's own assets/Final/mc.obj (a copy under tests/golden/ref_assets,
+    with its MTL and the PNGs that names) decodes its PNG
     maps (4-bit palette, gray, RGBA) but its materials are Disney BSDFs
     (no Pm / Tf, obj.rs:299-311): out of scope, RT_EUNSUPPORTED in both."""
-    path = "/root/reference/assets/Final/mc.obj"
-    if not os.path.exists(path):
-        pytest.skip("reference assets not mounted")
+    path = os.path.join(REF_ASSETS, "mc.obj")
     for api in (product, oracle):
         s = rt.Scene(api)
         with pytest.raises(capi.RtError) as e:

@@ -89,10 +89,9 @@ def test_camera_from_json_errors(product, rt, capi, tmp_path, edit):
     assert e.value.code == -1
 
 
-REF_CAMERA = "/root/reference/assets/Final/camera.json"
+REF_CAMERA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_assets", "camera.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CAMERA), reason="reference assets not present (GPU box)")
 def test_reference_camera_json(product, rt):
-    """The reference's own camera file (read in place), against Python's json."""
+    """The reference's own camera file (a copy under tests/golden), against Python's json."""
     check_camera(rt.Camera.from_json(product, REF_CAMERA), json.load(open(REF_CAMERA)))

@@ -19,7 +19,7 @@ import sys
 
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, no_aslr
 
 PKG_DIR = os.path.join(ROOT, "raytracer-2025_amd")
 ORC_DIR = os.path.join(ROOT, "oracle")
@@ -49,7 +49,7 @@ def _run(exe, obj, out, *extra, timeout=600):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", TSAN_OPTIONS="halt_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1")
     return subprocess.run([exe, obj, str(out), "8", "4", *extra], capture_output=True, text=True, timeout=timeout,
-                          env=env)
+                          env=env, preexec_fn=no_aslr)
 
 
 @pytest.mark.parametrize("which", ["product", "oracle"])
