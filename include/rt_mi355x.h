@@ -281,6 +281,21 @@ int32_t rt_render_partials_get(rt_scene* s, double* out, uint64_t n_values);
  * ln / acos / atan2 = glibc's); impl 1: ROCm's device libm (ocml).  Blocking. */
 int32_t rt_math_selftest(int32_t fn, int32_t impl, const double* a, const double* b, double* out, uint64_t n);
 
+/* Test hook (parity tooling, not part of the reference surface): n cases of
+ * one f32 stage of the closest-hit walk on the current gfx950 device -- the
+ * device functions the path kernels call -- from the host array `in` into
+ * `out`, a fixed number of doubles per case; f32 quantities travel as doubles
+ * that hold an f32 exactly.  fn (doubles in -> doubles out):
+ *   0  box test: o[3], d[3], lo[3], hi[3], tmin_f, c_f -> hit (0 / 1), entry
+ *   1  sphere filter: o[3], d[3], cx, cy, cz, r, g, c_f -> keep (0 / 1), c_f'
+ *   2  the f32 reciprocal of the ray set-up: x -> r
+ *   3  the f32 square root of the sphere filter's set-up: x -> r
+ *   4  the closest hit's f32 bound set from t: t -> c_f
+ *   5  that bound lowered by a hit t from c_f: t, c_f -> c_f'
+ *   6  the largest f32 <= x: x -> r
+ * Blocking. */
+int32_t rt_walk_selftest(int32_t fn, const double* in, double* out, uint64_t n);
+
 /* Test hook (host only, not part of the reference surface): builds
  * BVH::from_vec (bvh.rs:16-46) over the children of `list` twice, on copies
  * of the scene -- the parallel builder rt_bvh_new uses and the plain serial

@@ -128,6 +128,7 @@ SIGNATURES = {
     "world_info_get": (_I, [_P, _I, _I, _I, _U, C.POINTER(RtWorldInfo)]),
     "render_partials_get": (_I, [_P, _DP, C.c_uint64]),
     "math_selftest": (_I, [_I, _I, _DP, _DP, _DP, C.c_uint64]),
+    "walk_selftest": (_I, [_I, _DP, _DP, C.c_uint64]),
     "bvh_selftest": (_I, [_P, _I]),
     "world_selftest": (_I, [_P, _I, _I, _I]),
     "comm_unique_id": (_I, [C.POINTER(C.c_uint8)]),
@@ -137,7 +138,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("render_gather_mode", "render_partials_get", "math_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -143,6 +143,11 @@ extern "C" hipError_t rtk_launch_deinterleave_u8(const uint8_t* staging, size_t 
 extern "C" hipError_t rtk_launch_to_rgb(const float* lin, uint8_t* srgb, uint64_t n, int toon, hipStream_t stream);
 extern "C" hipError_t rtk_launch_math(int fn, int impl, const double* a, const double* b, double* out, uint64_t n,
                                       hipStream_t stream);
+// The walk self-test (rt_walk_selftest): fn's doubles per case in and out
+// (returns 0 for an unknown fn), and n cases through the device functions of
+// the f32 walk stages, from device arrays.
+extern "C" int rtk_walk_widths(int fn, int* in_w, int* out_w);
+extern "C" hipError_t rtk_launch_walk(int fn, const double* in, double* out, uint64_t n, hipStream_t stream);
 // device bytes rtk_launch_frame needs at params_dev
 extern "C" size_t rtk_params_bytes(void);
 extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu);

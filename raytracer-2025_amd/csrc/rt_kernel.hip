@@ -3230,8 +3230,10 @@ extern "C" int rtk_occupancy_4(int*);
 
 namespace rtk {
 // Color::to_rgb (utils/color.rs:14-36): optional ACES fit, clamp, then the sRGB
-// OETF and f64 -> u8 (palette restated as in oracle/rt_oracle.cpp to_rgb;
-// parity unpinned).  No contraction, so the arithmetic is the host's.
+// OETF and f64 -> u8 (palette restated as in oracle/rt_oracle.cpp to_rgb).
+// No contraction, so the arithmetic is the host's; pow is ocml's.  Held to
+// the exact byte of the real-valued function on every f32 input that is not
+// within a relative 2^-40 of a byte boundary (tests/test_to_rgb_gpu.py).
 __device__ __forceinline__ uint8_t srgb_u8(double x, int toon) {
 #pragma clang fp contract(off)
     if (toon == 1) {
@@ -3376,6 +3378,61 @@ __global__ void __launch_bounds__(256) rt_math_kernel(int fn, int impl, const do
         }
     }
     out[i] = r;
+}
+
+// Walk self-test (rt_walk_selftest): the f32 stages of the closest-hit walk --
+// the very functions the path kernels call -- one case per thread, in_w
+// doubles in and out_w out per case (rtk_walk_widths).  f32 quantities
+// travel as doubles that hold an f32 exactly, so the casts below are exact.
+__global__ void __launch_bounds__(256) rt_walk_kernel(int fn, int in_w, int out_w, const double* __restrict__ in,
+                                                     double* __restrict__ out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* p = in + i * (uint64_t)in_w;
+    double* q = out + i * (uint64_t)out_w;
+    switch (fn) {
+        case 0: {  // o[3], d[3], lo[3], hi[3], tmin_f, c_f -> hit, entry
+            const double o[3] = {p[0], p[1], p[2]}, d[3] = {p[3], p[4], p[5]};
+            const float lo[3] = {(float)p[6], (float)p[7], (float)p[8]}, hi[3] = {(float)p[9], (float)p[10], (float)p[11]};
+            const RayF R = make_rayf(o, d);
+            float entry = 0.0f;
+            const bool hit = slab_f(lo, hi, R, (float)p[12], (float)p[13], entry);
+            q[0] = hit ? 1.0 : 0.0;
+            q[1] = (double)entry;
+            break;
+        }
+        case 1: {  // o[3], d[3], cx, cy, cz, r, g, c_f -> keep, c_f'
+            const double o[3] = {p[0], p[1], p[2]}, d[3] = {p[3], p[4], p[5]};
+            const SphF F = make_sphf(o, d);
+            float c_f = (float)p[11];
+            const bool keep = sphere_filter((float)p[6], (float)p[7], (float)p[8], (float)p[9], (float)p[10], F, c_f, true);
+            q[0] = keep ? 1.0 : 0.0;
+            q[1] = (double)c_f;
+            break;
+        }
+        case 2: q[0] = (double)rcp_f32((float)p[0]); break;
+        case 3: {
+            float r;
+            sqrt_f32((float)p[0], r);
+            q[0] = (double)r;
+            break;
+        }
+        case 4: {
+            Closest cl;
+            cl.set(p[0]);
+            q[0] = (double)cl.c_f;
+            break;
+        }
+        case 5: {
+            Closest cl;
+            cl.c = 0.0;
+            cl.c_f = (float)p[1];
+            cl.lower(p[0]);
+            q[0] = (double)cl.c_f;
+            break;
+        }
+        default: q[0] = (double)f32_down(p[0]); break;
+    }
 }
 
 // to_rgb of a linear f32 framebuffer already on the device (e.g. the gathered
@@ -3560,6 +3617,24 @@ extern "C" hipError_t rtk_launch_math(int fn, int impl, const double* a, const d
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(rtk::rt_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fn, impl, a, b, out,
                        n);
+    return hipGetLastError();
+}
+
+// doubles per case of walk self-test fn (0 for an unknown fn)
+extern "C" int rtk_walk_widths(int fn, int* in_w, int* out_w) {
+    static const int IN[7] = {14, 12, 1, 1, 1, 2, 1}, OUT[7] = {2, 2, 1, 1, 1, 1, 1};
+    if (fn < 0 || fn > 6) return 0;
+    *in_w = IN[fn];
+    *out_w = OUT[fn];
+    return 1;
+}
+
+extern "C" hipError_t rtk_launch_walk(int fn, const double* in, double* out, uint64_t n, hipStream_t stream) {
+    int in_w = 0, out_w = 0;
+    if (!rtk_walk_widths(fn, &in_w, &out_w)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rtk::rt_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fn, in_w, out_w, in,
+                       out, n);
     return hipGetLastError();
 }
 

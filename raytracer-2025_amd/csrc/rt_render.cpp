@@ -1176,6 +1176,31 @@ int32_t rt_math_selftest(int32_t fn, int32_t impl, const double* a, const double
     return rc;
 }
 
+int32_t rt_walk_selftest(int32_t fn, const double* in, double* out, uint64_t n) {
+    int in_w = 0, out_w = 0;
+    if (!rtk_walk_widths(fn, &in_w, &out_w)) return set_error(RT_EINVAL, "unknown function");
+    if (n && (!in || !out)) return set_error(RT_EINVAL, "null argument");
+    if (n == 0) return RT_OK;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return set_error(RT_EDEVICE, std::string("librt_mi355x.so needs a gfx950 device, found ") + prop.gcnArchName);
+    double* d = nullptr;
+    const size_t in_bytes = n * in_w * sizeof(double), out_bytes = n * out_w * sizeof(double);
+    if ((e = hipMalloc(&d, in_bytes + out_bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    double* d_out = d + n * in_w;
+    int32_t rc = RT_OK;
+    if ((e = hipMemcpy(d, in, in_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = rtk_launch_walk(fn, d, d_out, n, nullptr)) != hipSuccess ||
+        (e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = hip_fail(e, "walk self-test");
+    (void)hipFree(d);
+    return rc;
+}
+
 int32_t rt_render(rt_scene* s, int32_t world, int32_t lights, const rt_camera* cam, const rt_render_opts* opts,
                   float* out_lin, uint8_t* out_srgb, rt_stats* st) {
     if (!cam) return set_error(RT_EINVAL, "null camera");

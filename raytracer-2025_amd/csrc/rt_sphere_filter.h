@@ -1,9 +1,10 @@
 // rt_sphere_filter.h -- the basic tier's conservative f32 sphere test.
 //
 // Host and device: the kernel (rt_kernel.hip visit4) runs it, and the CPU
-// property test (tests/test_filter_cpu.py, tests/filter_prop.cpp) checks it
-// against the exact f64 Sphere::hit (sphere.rs:77-108) on random and
-// adversarial rays.
+// property test (tests/test_filter_cpu.py, tests/cpp/filter_prop.cpp) checks
+// it against the exact f64 Sphere::hit (sphere.rs:77-108) on random and
+// adversarial rays; tests/test_walk_filters_gpu.py runs the same cases through
+// the device build (rt_walk_selftest).
 //
 // Reference algorithm (sphere.rs:77-96): oc = c - o, a = |d|^2, h = d.oc,
 // cc = |oc|^2 - r^2, disc = h^2 - a cc; hit at the near root (h - sqrt(disc))/a
@@ -61,11 +62,9 @@ RT_HD SphF make_sphf(const double o[3], const double d[3]) {
 #if RT_RCP_F32 == 2
     // the hardware square root and reciprocal (1 ulp): ehd's 2^-19 is five
     // times the 6.2u bound it scales, and ia's margin of 2^-19 is 16 ulps
-#if defined(__HIP_DEVICE_COMPILE__)
-    F.ehd = __builtin_amdgcn_sqrtf(F.a) * 0x1p-19f;
-#else
-    F.ehd = std::sqrt(F.a) * 0x1p-19f;
-#endif
+    float sq;
+    sqrt_f32(F.a, sq);
+    F.ehd = sq * 0x1p-19f;
     F.ia = rcp_f32(F.a) * (1.0f + 0x1p-19f);
 #else
     F.ehd = sqrtf(F.a) * 0x1p-19f;

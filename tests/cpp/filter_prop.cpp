@@ -6,10 +6,17 @@
 //   (a) filter rejects             => t is none or t > c_f (the bound it got)
 //   (b) filter lowers c_f to c_f'  => t exists and t <= c_f'
 //   (c) c_f' <= c_f always
+// Direction components are also -0.0, f32-subnormal (1e-40) or zero in f32
+// (1e-300), either sign.
 // Prints "cases rejected lowered violations" and exits 1 on any violation.
+// filter_prop [n [seed]] [--dump FILE]: with --dump every case is also written
+// to FILE as 15 doubles -- o[3], d[3], cx, cy, cz, r, g, c_f exactly as handed
+// to the f32 code (the sphere rounded to f32, g rounded up; rt_walk_selftest's
+// fn 1 input), the exact root t (-1 = none), and this build's own keep and c_f'.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 
 #include "../../raytracer-2025_amd/csrc/rt_sphere_filter.h"
@@ -24,8 +31,19 @@ static float round_up_f(double x) {
 }
 
 int main(int argc, char** argv) {
-    const long n = argc > 1 ? std::atol(argv[1]) : 2000000;
-    std::mt19937_64 rng(argc > 2 ? std::atoll(argv[2]) : 2025);
+    const char* dump_path = nullptr;
+    const char* pos[2] = {nullptr, nullptr};
+    for (int i = 1, np = 0; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump_path = argv[++i];
+        else if (np < 2) pos[np++] = argv[i];
+    }
+    const long n = pos[0] ? std::atol(pos[0]) : 2000000;
+    std::mt19937_64 rng(pos[1] ? std::atoll(pos[1]) : 2025);
+    FILE* dump = dump_path ? std::fopen(dump_path, "wb") : nullptr;
+    if (dump_path && !dump) {
+        std::perror(dump_path);
+        return 2;
+    }
     std::uniform_real_distribution<double> U(0.0, 1.0);
     auto unit = [&](double v[3]) {
         double z = 1 - 2 * U(rng), r = std::sqrt(std::fmax(0.0, 1 - z * z)), p = 2 * M_PI * U(rng);
@@ -73,6 +91,12 @@ int main(int argc, char** argv) {
         }
         const double len = std::exp(std::log(1e-2) + U(rng) * std::log(1e4));  // |d| in [0.01, 100]
         for (int k = 0; k < 3; ++k) d[k] *= len;
+        // a component that is -0.0, subnormal in f32 or zero in f32 (after the scaling)
+        const int zk = (int)(U(rng) * 10);
+        if (zk < 3) {
+            static const double tiny[3] = {0.0, 1e-40, 1e-300};
+            d[(int)(U(rng) * 3)] = U(rng) < 0.5 ? -tiny[zk] : tiny[zk];
+        }
         const double tx = exact_sphere_t(c, r, o, d, 1e-8, INFINITY);
         // the walk's bound: none, random, or right at the exact root
         float cf = INFINITY;
@@ -84,6 +108,10 @@ int main(int argc, char** argv) {
         const float g = round_up_f(std::fabs((double)cx) + std::fabs((double)cy) + std::fabs((double)cz) + std::fabs((double)rf));
         float cf2 = cf;
         const bool keep = rtk::sphere_filter(cx, cy, cz, rf, g, F, cf2, true);
+        if (dump) {
+            const double rec[15] = {o[0], o[1], o[2], d[0], d[1], d[2], cx, cy, cz, rf, g, cf, tx, keep ? 1.0 : 0.0, cf2};
+            std::fwrite(rec, sizeof rec, 1, dump);
+        }
         bool ok_case = cf2 <= cf || (std::isnan(cf) && std::isnan(cf2));
         if (!keep) {
             ++rejected;
@@ -101,6 +129,7 @@ int main(int argc, char** argv) {
             ++bad;
         }
     }
+    if (dump && std::fclose(dump) != 0) return 2;
     std::printf("%ld %ld %ld %ld\n", n, rejected, lowered, bad);
     return bad ? 1 : 0;
 }

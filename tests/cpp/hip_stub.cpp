@@ -385,4 +385,7 @@ hipError_t rtk_launch_math(int, int, const double*, const double*, double*, uint
     return hipErrorNotSupported;
 }
 
+int rtk_walk_widths(int, int*, int*) { return 0; }
+hipError_t rtk_launch_walk(int, const double*, double*, uint64_t, hipStream_t) { return hipErrorNotSupported; }
+
 }  // extern "C"

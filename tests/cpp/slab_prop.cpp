@@ -6,11 +6,18 @@
 // down and c rounded up, must admit it too.  Random and adversarial rays and
 // boxes: origins on faces, edges and corners, grazing rays along a face,
 // zero direction components, flat boxes, boxes far from the origin, tiny and
-// huge boxes, c right at the box entry.
+// huge boxes, c right at the box entry; direction components that are -0.0,
+// f32-subnormal (1e-40) or zero in f32 (1e-300), either sign.
 // Prints "cases exact_hits f32_hits violations"; exits 1 on any violation.
+// slab_prop [n [seed]] [--dump FILE]: with --dump every case that is not
+// skipped is also written to FILE as 17 doubles -- o[3], d[3], lo[3], hi[3],
+// tmin_f, c_f exactly as handed to the f32 code (the box rounded outward,
+// t_min down, c up; the first 14 are rt_walk_selftest's fn 0 input), the
+// exact verdict, and this build's own hit and entry.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 
 #include "../../raytracer-2025_amd/csrc/rt_slab.h"
@@ -43,8 +50,19 @@ static int exact(const double lo[3], const double hi[3], const double o[3], cons
 }
 
 int main(int argc, char** argv) {
-    const long n = argc > 1 ? std::atol(argv[1]) : 2000000;
-    std::mt19937_64 rng(argc > 2 ? std::atoll(argv[2]) : 2025);
+    const char* dump_path = nullptr;
+    const char* pos[2] = {nullptr, nullptr};
+    for (int i = 1, np = 0; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump_path = argv[++i];
+        else if (np < 2) pos[np++] = argv[i];
+    }
+    const long n = pos[0] ? std::atol(pos[0]) : 2000000;
+    std::mt19937_64 rng(pos[1] ? std::atoll(pos[1]) : 2025);
+    FILE* dump = dump_path ? std::fopen(dump_path, "wb") : nullptr;
+    if (dump_path && !dump) {
+        std::perror(dump_path);
+        return 2;
+    }
     std::uniform_real_distribution<double> U(0.0, 1.0);
     long hits = 0, fhits = 0, bad = 0;
     for (long i = 0; i < n; ++i) {
@@ -89,6 +107,12 @@ int main(int argc, char** argv) {
         if (dk == 2) d[(int)(U(rng) * 3)] = 0.0;
         const double len = std::exp(std::log(1e-3) + U(rng) * std::log(1e6));
         for (int k = 0; k < 3; ++k) d[k] *= len;
+        // a component that is -0.0, subnormal in f32 or zero in f32 (after the scaling)
+        const int zk = (int)(U(rng) * 10);
+        if (zk < 3) {
+            static const double tiny[3] = {0.0, 1e-40, 1e-300};
+            d[(int)(U(rng) * 3)] = U(rng) < 0.5 ? -tiny[zk] : tiny[zk];
+        }
         if (d[0] == 0 && d[1] == 0 && d[2] == 0) continue;
         const double tmin = 1e-8;
         double c = INFINITY;
@@ -114,7 +138,13 @@ int main(int argc, char** argv) {
         }
         const rtk::RayF R = rtk::make_rayf(o, d);
         float entry;
-        const bool f = rtk::slab_f(flo, fhi, R, rtk::f32_down(tmin), up(c), entry);
+        const float tmin_f = rtk::f32_down(tmin), c_f = up(c);
+        const bool f = rtk::slab_f(flo, fhi, R, tmin_f, c_f, entry);
+        if (dump) {
+            const double rec[17] = {o[0], o[1], o[2], d[0], d[1], d[2], flo[0], flo[1], flo[2], fhi[0], fhi[1], fhi[2],
+                                    tmin_f, c_f, (double)ex, f ? 1.0 : 0.0, entry};
+            std::fwrite(rec, sizeof rec, 1, dump);
+        }
         hits += ex;
         fhits += f;
         if (ex == 1 && !f) {
@@ -125,6 +155,7 @@ int main(int argc, char** argv) {
             ++bad;
         }
     }
+    if (dump && std::fclose(dump) != 0) return 2;
     std::printf("%ld %ld %ld %ld\n", n, hits, fhits, bad);
     return bad ? 1 : 0;
 }

@@ -132,6 +132,19 @@ def test_comm_and_partials_without_render(product, rt):
     assert product.render_partials_get(s.s, None, 0) == -1
 
 
+def test_walk_selftest_argument_checks(product):
+    """rt_walk_selftest refuses an unknown fn and null arrays before touching a
+    device, and n = 0 is a no-op."""
+    one = (ctypes.c_double * 14)()
+    for fn in (-1, 7):
+        assert product.walk_selftest(fn, one, one, 1) == -1
+        assert b"unknown function" in product.last_error()
+    assert product.walk_selftest(0, None, one, 1) == -1
+    assert product.walk_selftest(0, one, None, 1) == -1
+    for fn in range(7):
+        assert product.walk_selftest(fn, None, None, 0) == 0
+
+
 def test_render_opts_struct_size_checked(product, rt, scenes, capi):
     """rt_render_opts carries its size (ABI 3): options not made by
     rt_render_opts_default (struct_size 0, an older and smaller struct) are

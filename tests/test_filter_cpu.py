@@ -6,8 +6,10 @@ the sphere's surface and a hair off it, tangent rays, rays aimed at the rim,
 the book-1 ground sphere (r = 1000), tiny and far spheres, |d| over four
 decades, bounds right at the exact root.  The filter may only reject spheres
 whose exact hit is absent or beyond the bound, and may only lower the bound to
-a value >= the exact hit (tests/cpp/filter_prop.cpp).  Built twice: with FMA
-contraction of the f32 code (as the GPU compiles it) and without."""
+a value >= the exact hit (tests/cpp/filter_prop.cpp).  Built twice: without
+FMA contraction, as the kernel is built (-ffp-contract=off; the filter's own
+fmaf calls stay), and with it, so the property does not hang on that flag.
+The same cases run on the device in tests/test_walk_filters_gpu.py."""
 import os
 import subprocess
 
