@@ -29,8 +29,10 @@
 namespace rtk {
 
 // Basic tier: 4-wide BVH nodes (rth::bvh4_convert), sphere children through
-// the f32 filter (rt_sphere_filter.h) into a per-lane LDS queue of exact tests
-// (visit4); 0 = two-box nodes with inline f64 sphere tests.
+// the slab test of their own f32 box (rt_slab.h sphere_box_f) into a per-lane
+// LDS queue of exact tests (visit4_rows); 0 = two-box nodes with inline f64
+// sphere tests.  (rt_sphere_filter.h is no longer called by the path kernels:
+// only rt_walk_selftest runs it.)
 #ifndef RT_BVH4
 #define RT_BVH4 1
 #endif
@@ -595,7 +597,7 @@ struct Closest {
         const float f = (float)t;
         c_f = fmaf(fabsf(f), 1.1920928955078125e-07f, f);
     }
-    // a hit t <= c found while c_f may already be a tighter bound (sphere filter)
+    // a hit t <= c that never loosens c_f (basic tier's sphere rounds)
     __device__ __forceinline__ void lower(double t) {
         c = t;
         const float f = (float)t;
@@ -912,8 +914,7 @@ struct Trav {
     bool found;
     HitInfo hit;
     uint32_t nmed;  // FULL: media met by the walk, tested after it (media_phase)
-    SphF sf;        // BASIC (4-wide): the sphere filter's per-ray f32 data
-    uint32_t pn;    // and the number of spheres queued for the exact test
+    uint32_t pn;    // BASIC (4-wide): the number of spheres queued for the exact test
 };
 
 template <int TIER>
@@ -931,8 +932,6 @@ __device__ __forceinline__ void trace_begin(const SceneView& S, const Ray& wr, T
     T.hit.nxf = 0;
     T.nmed = 0;
     if constexpr (TIER == TIER_BASIC && RT_BVH4) {
-        const double o[3] = {wr.o.x, wr.o.y, wr.o.z}, d[3] = {wr.d.x, wr.d.y, wr.d.z};
-        T.sf = make_sphf(o, d);
         T.pn = 0;
         T.cur = bword(S, S.world_root);  // the 4-wide walk's cur is a walk word
     }
@@ -998,8 +997,6 @@ __device__ __forceinline__ void trace_ray_fields(const Ray& wr, Trav<TIER_BASIC>
     T.rf = make_rayf(wr);
     T.a = len2(wr.d);
     T.inva = 1.0 / T.a;
-    const double o[3] = {wr.o.x, wr.o.y, wr.o.z}, d[3] = {wr.d.x, wr.d.y, wr.d.z};
-    T.sf = make_sphf(o, d);
 }
 // The world-frame ray as the walk reads it: a register copy, or (full-flat
 // tier) the lane's LDS copy, read only where a walk step
@@ -1287,8 +1284,8 @@ __device__ __forceinline__ void media_phase(const SceneView& S, const WR& wrr, T
 // one of them when at most RT_DEFER_THIN are: a wave thinned out at the end
 // of a launch tests its queued spheres at once instead of walking on with an
 // unbounded walk (a ray trapped in a glass sphere queues the sphere it starts
-// on at every bounce: its origin is on the surface, so the filter can bound
-// nothing).  Measured within noise on the whole frame and on the 1/8 shard:
+// on at every bounce: its origin is on the surface, inside the sphere's box).
+// Measured within noise on the whole frame and on the 1/8 shard:
 // the slow last waves of the lane trace were the exit atomics' (the kernel's
 // end), not this.
 #ifndef RT_DEFER_THIN
@@ -1296,10 +1293,15 @@ __device__ __forceinline__ void media_phase(const SceneView& S, const WR& wrr, T
 #endif
 
 // ------------------------------------------------------------------ basic tier: 4-wide BVH
-// One visit of a DNode4: the sphere children's f32 filter (queued into the
-// lane's LDS queue, pq[k * RT_BLOCK_BASIC], when the exact test must run), then the
-// four slab tests; the hit boxes are sorted by entry distance, the nearest is
-// walked next and the others pushed farthest first.
+// One visit of a DNode4: four slab tests; a sphere child whose box is hit is
+// queued for its exact test (the lane's LDS queue, pq[k * RT_BLOCK_BASIC]);
+// the hit box children are sorted by entry distance, the nearest is walked
+// next and the others pushed farthest first.  (Until round 7 a sphere child
+// went through the f32 sphere filter of rt_sphere_filter.h instead: about 30
+// VALU instructions a slot beside the slab's 19, and eleven per-ray registers;
+// the box admits more rays -- 1.88 exact tests a ray on C2 instead of 1.49 --
+// and gives the walk no early bound -- 5.32 node visits a ray instead of 5.01
+// -- yet C2 is 3.5 % faster: profiles/r07/ab_boxed_spheres_c2_128spp.json.)
 struct Node4Rows {
     float4 lx, ly, lz, hx, hy, hz, rq;
 };
@@ -1319,8 +1321,8 @@ __device__ __forceinline__ Node4Rows load_node4(const RT_LDS float4* nl, uint32_
 #endif
 // visit4 on node rows already loaded; the ref row holds walk words (bword)
 template <class Stack>
-__device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4Rows& nr, const RayF& rf, const SphF& sf, float tmin_f,
-                                                float& c_f, Stack& stk, uint32_t& sp, RT_LDS uint16_t* pq, uint32_t& pn) {
+__device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4Rows& nr, const RayF& rf, float tmin_f,
+                                                float c_f, Stack& stk, uint32_t& sp, RT_LDS uint16_t* pq, uint32_t& pn) {
     const float4 lx = nr.lx, ly = nr.ly, lz = nr.lz, hx = nr.hx, hy = nr.hy, hz = nr.hz, rq = nr.rq;
     const float LX[4] = {lx.x, lx.y, lx.z, lx.w}, LY[4] = {ly.x, ly.y, ly.z, ly.w}, LZ[4] = {lz.x, lz.y, lz.z, lz.w};
     const float HX[4] = {hx.x, hx.y, hx.z, hx.w}, HY[4] = {hy.x, hy.y, hy.z, hy.w}, HZ[4] = {hz.x, hz.y, hz.z, hz.w};
@@ -1328,29 +1330,24 @@ __device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4R
     constexpr float INF = __builtin_huge_valf();
     float key[4];
     uint32_t ref[4];
-    // per slot, the filter / slab only when some lane has a sphere / a box
-    // there: the flatten puts a node's spheres in its low slots and its empty
-    // slots last (rth::bvh4_convert), and most leaf-level nodes hold 2-3 spheres
+    // per slot, one slab test when some lane has a child there: a sphere
+    // child's row holds its own box (rth::bvh4_convert), and a hit queues it
+    // for the exact test where a box child's hit gets its sort key.  The
+    // flatten puts a node's empty slots last.
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        bool sph = (uint16_t)R[i] != 0;
-        if (__ballot(sph)) {
-            if (sphere_filter(LX[i], LY[i], LZ[i], HX[i], HY[i], sf, c_f, sph)) {
+        const bool sph = (uint16_t)R[i] != 0, box = R[i] > 0xffffu;
+        key[i] = INF;
+        ref[i] = R[i];
+        if (__ballot(sph || box)) {
+            const float lo[3] = {LX[i], LY[i], LZ[i]}, hi[3] = {HX[i], HY[i], HZ[i]};
+            float e;
+            const bool h = slab_f(lo, hi, rf, tmin_f, c_f, e);
+            if (h && sph) {
                 pq[pn * RT_BLOCK_BASIC] = (uint16_t)(R[i] & 0x7fffu);
                 ++pn;
             }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const bool box = R[i] > 0xffffu;
-        key[i] = INF;
-        ref[i] = R[i];
-        if (__ballot(box)) {
-            const float lo[3] = {LX[i], LY[i], LZ[i]}, hi[3] = {HX[i], HY[i], HZ[i]};
-            float e;
-            const bool h = slab_f(lo, hi, rf, tmin_f, c_f, e) && box;
-            key[i] = h ? e : INF;
+            key[i] = h && box ? e : INF;
         }
     }
     // no lane of the wave hit a box child (nodes of spheres only, or every
@@ -1451,7 +1448,12 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
                                             RT_LDS uint16_t* pq, const RT_LDS float4* nl, Diag& dg) {
     constexpr double tmin = 1e-8;
     const float tmin_f = f32_down(tmin);
-    constexpr uint32_t ROOM = RT_PEND_CAP - 4;  // a visit queues at most 4
+    // a visit queues at most 4 (one per slot), and a lane visits only with
+    // pn <= ROOM: the lane's LDS queue never overflows.  (A lane that waits
+    // for its round with any sphere queued, ROOM = 0, so that the bound comes
+    // before the next node: C2 +16.6 %, profiles/r07/ab_boxed_spheres_c2_128spp.json)
+    static_assert(RT_PEND_CAP >= 4, "a visit may queue 4 spheres: the lane's LDS queue must hold them");
+    constexpr uint32_t ROOM = RT_PEND_CAP - 4;
     RT_DIAG_ONLY(if (__lane_id() == (uint32_t)(__ffsll((long long)__ballot(true)) - 1)) ++dg.wave_trace_iters;)
     uint32_t pn = T.pn;
     // The sphere round is decided on the state before this step's node
@@ -1520,7 +1522,7 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
     if (node) {
         RT_ISA_MARK("walk_visit");
         RT_DIAG_ONLY(++dg.node_visits;)
-        T.cur = visit4_rows(S, rows, T.rf, T.sf, tmin_f, T.cl.c_f, stk, T.sp, pq, pn);
+        T.cur = visit4_rows(S, rows, T.rf, tmin_f, T.cl.c_f, stk, T.sp, pq, pn);
     }
     // the sphere round's f64 test after the node visit: the visit's LDS rows
     // arrive before the sphere's global load, and the test then finds it

@@ -80,9 +80,9 @@ static_assert(sizeof(DNode) == 80, "DNode must be 80 B (5 dwordx4)");
 
 // Basic-tier 4-wide BVH node (rth::bvh4_basic): up to four children, their
 // f32 boxes (rounded outward) stored component-major so one dwordx4 holds one
-// bound of all four.  A sphere child keeps the sphere filter's record in its
-// box slots instead: lo = center, hi.x = radius, hi.y = g = |c|_1 + r rounded
-// up (rt_sphere_filter.h), all rounded to nearest but g.
+// bound of all four.  A sphere child's box is its own, c -+ r widened by a hair
+// and rounded outward (rt_slab.h sphere_box_f): the walk slab-tests it like any
+// other child's and queues the sphere for the exact f64 test on a hit.
 struct alignas(16) DNode4 {
     float lo[3][4], hi[3][4];
     uint32_t ref[4];  // REF_NONE for an unused slot

@@ -3,6 +3,7 @@
 #include "rt_kernel.h"
 #include "rt_image.hpp"
 #include "rt_scene.hpp"
+#include "rt_slab.h"
 
 #include <algorithm>
 #include <cstring>
@@ -1530,7 +1531,8 @@ constexpr uint32_t BVH4_TOP = 341;  // 1 + 4 + 16 + 64 + 256
 // replaced by its own children until there are four or no inner child is left
 // (the usual top-down BVH2 -> BVH4 collapse).  Child boxes are the parents' f32
 // boxes, already rounded outward.  filter_spheres (basic tier): sphere children
-// become filter records and are queued, not stacked, so need(node) = (inner
+// get their own box a hair wider than c -+ r (rt_slab.h sphere_box_f) and are
+// queued for their exact test on a box hit, not stacked, so need(node) = (inner
 // children - 1) + max need(inner child); otherwise (mesh tier) a sphere child
 // gets its box rounded outward and, like every child, is walked near-first
 // through the stack: need(node) = (children - 1) + max need(child).
@@ -1543,6 +1545,21 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
     };
     std::vector<rtk::DNode4> out;
     std::vector<uint32_t> map(hw.nodes.size(), REF_NONE);
+    // basic tier: the diagonal of the box round every sphere, a bound on the
+    // distance from any surface point (a scattered ray's origin) to any centre
+    double reach = 0.0;
+    if (filter_spheres && !hw.spheres.empty()) {
+        double wlo[3] = {INFINITY, INFINITY, INFINITY}, whi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const double4& sp : hw.spheres) {
+            const double c[3] = {sp.x, sp.y, sp.z}, r = std::fabs(sp.w);
+            for (int a = 0; a < 3; ++a) {
+                wlo[a] = std::fmin(wlo[a], c[a] - r);
+                whi[a] = std::fmax(whi[a], c[a] + r);
+            }
+        }
+        reach = std::sqrt((whi[0] - wlo[0]) * (whi[0] - wlo[0]) + (whi[1] - wlo[1]) * (whi[1] - wlo[1]) +
+                          (whi[2] - wlo[2]) * (whi[2] - wlo[2])) * (1.0 + 0x1p-50);
+    }
     auto kids = [&](uint32_t idx, std::vector<Child>& v) {
         const rtk::DNode& n = hw.nodes[idx];
         const uint32_t refs[2] = {n.c0, n.c1};
@@ -1586,8 +1603,8 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
         }
 #if RT_BVH4_SPHERES_FIRST
         // basic tier: sphere children in the low slots, boxes after them, empty
-        // slots last -- a wave tests a slot's filter / slab only when one of its
-        // lanes has that kind there (rt_kernel.hip visit4_rows); most leaf-level
+        // slots last -- a wave runs a slot's slab test only when one of its
+        // lanes has a child there (rt_kernel.hip visit4_rows); most leaf-level
         // nodes hold 2 or 3 spheres
         if (filter_spheres)
             std::stable_partition(ch.begin(), ch.end(),
@@ -1606,19 +1623,22 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
         }
         for (size_t i = 0; i < ch.size(); ++i) {
             uint32_t r = ch[i].ref;
+            if (rtk::ref_kind(r) == rtk::K_BVH) r = conv(rtk::ref_index(r));
+            for (int a = 0; a < 3; ++a) {
+                n.lo[a][i] = ch[i].lo[a];
+                n.hi[a][i] = ch[i].hi[a];
+            }
             if (filter_spheres && rtk::ref_kind(r) == rtk::K_SPHERE) {
+                // basic tier: the sphere's own box, a hair wider than c -+ r
+                // (rt_slab.h sphere_box_f: by the f64 test's slop for origins
+                // anywhere in the world), slab-tested like any other child's
                 const double4 sp = hw.spheres[rtk::ref_index(r)];
-                const float c[3] = {(float)sp.x, (float)sp.y, (float)sp.z}, rad = (float)sp.w;
-                for (int a = 0; a < 3; ++a) n.lo[a][i] = c[a];
-                n.hi[0][i] = rad;
-                n.hi[1][i] = round_up(std::fabs((double)c[0]) + std::fabs((double)c[1]) + std::fabs((double)c[2]) +
-                                      std::fabs((double)rad));
-                n.hi[2][i] = 0.0f;
-            } else {
-                if (rtk::ref_kind(r) == rtk::K_BVH) r = conv(rtk::ref_index(r));
+                const double s[4] = {sp.x, sp.y, sp.z, sp.w};
+                float lo[3], hi[3];
+                rtk::sphere_box_f(s, reach, lo, hi);
                 for (int a = 0; a < 3; ++a) {
-                    n.lo[a][i] = ch[i].lo[a];
-                    n.hi[a][i] = ch[i].hi[a];
+                    n.lo[a][i] = lo[a];
+                    n.hi[a][i] = hi[a];
                 }
             }
             n.ref[i] = r;

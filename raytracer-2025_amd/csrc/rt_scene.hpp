@@ -158,8 +158,9 @@ int32_t set_error(int32_t code, const std::string& msg);
 // the binned-SAH rebuild (closest-hit results agree up to exact t ties).
 int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, bool reference_bvh,
                 HostWorld& out);
-// Collapses every two-box BVH into 4-wide nodes (hw.nodes4; sphere children as
-// filter records when filter_spheres, the basic tier), rewrites the K_BVH refs
+// Collapses every two-box BVH into 4-wide nodes (hw.nodes4; sphere children with
+// their own padded box, queued not stacked, when filter_spheres: the basic
+// tier), rewrites the K_BVH refs
 // to index nodes4 and recomputes stack_need.  Returns the new stack_need (hw is
 // unchanged when it exceeds max_need), or UINT32_MAX (hw unchanged) when the
 // tree would have more than max_nodes nodes.

@@ -159,6 +159,44 @@ RT_HD float f32_down(double x) {
     return f;
 }
 
+// The f32 box of a basic-tier sphere child {cx, cy, cz, r} (rth::bvh4_convert):
+// the walk slab-tests it and runs the exact f64 Sphere::hit (sphere.rs:77-108)
+// only on a hit, so the box must hold every point that test can return -- and
+// the f64 test has a slop of its own.  With u = 2^-53 and M = 2 |c - o| + r its
+// discriminant is off by less than 32 u |d|^2 M^2, so a root it accepts lies
+// within r + 16 u M^2 / r of the centre: outside the sphere by a hair when
+// the ray grazes it.  Where the graze is at a pole, on a face of the exact box,
+// and the f32 roundings happen to leave no slack (c +- r exact in f32, the
+// origin's coordinate zero), a ray in that face's plane would be culled and
+// the image change.  So the radius is widened before rounding outward, by the
+// larger of
+//   2^-16 r: the slop for every origin within 4.6e4 radii of the centre
+//     (2^-16 >= 16 u (M / r)^2 for M / r <= 2^16.5), which is every sphere of
+//     an ordinary world and costs no measurable false positives, and
+//   16 u (2 reach + r)^2 / r: the slop for every origin within reach of the
+//     centre.  The flatten passes the diagonal of the world's bounding box, so
+//     this holds for every scattered ray, whose origin lies on a surface of
+//     the world; it is the larger term only for a sphere more than 2.3e4 times
+//     smaller than the world.
+// A sphere so small that the pad would exceed reach (r = 0 included) gets
+// c -+ (r + reach), which holds the whole world: a ray from inside it always
+// hits.  What is left to the caller is the camera: a primary ray's origin
+// outside the world's box is covered only within max(reach, 4.6e4 r) of the
+// centre.  tests/test_sphere_box_cpu.py holds the property.
+RT_HD void sphere_box_f(const double s[4], double reach, float lo[3], float hi[3]) {
+    const double r = s[3], M = 2.0 * reach + r;
+    double pad = r * 0x1p-16;
+    const double far = 0x1p-49 * M * M / r;  // 16 u M^2 / r
+    if (far > pad) pad = far;
+    if (!(pad <= reach)) pad = reach;  // (also r = 0: far is inf or NaN)
+    if (!(pad >= r * 0x1p-16)) pad = r * 0x1p-16;  // (reach < 2^-16 r: a one-sphere world)
+    const double m = r + pad;
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = f32_down(s[k] - m);
+        hi[k] = -f32_down(-(s[k] + m));
+    }
+}
+
 // Entry distance (clamped to t_min) and hit of box [lo, hi] for t in [tmin_f, c_f].
 RT_HD bool slab_f(const float* lo, const float* hi, const RayF& R, float tmin_f, float c_f, float& entry) {
 #if RT_SLAB_FOLD

@@ -1,10 +1,14 @@
 // rt_sphere_filter.h -- the basic tier's conservative f32 sphere test.
 //
-// Host and device: the kernel (rt_kernel.hip visit4) runs it, and the CPU
-// property test (tests/test_filter_cpu.py, tests/cpp/filter_prop.cpp) checks
-// it against the exact f64 Sphere::hit (sphere.rs:77-108) on random and
-// adversarial rays; tests/test_walk_filters_gpu.py runs the same cases through
-// the device build (rt_walk_selftest).
+// The path kernels no longer call it: since round 7 a sphere child of a basic-
+// tier node carries its own f32 box and is slab-tested like any other child
+// (rt_slab.h sphere_box_f, rt_kernel.hip visit4_rows), which costs fewer VALU
+// instructions a visit than this filter did.  The functions stay, host and
+// device, with their tests: the CPU property test (tests/test_filter_cpu.py,
+// tests/cpp/filter_prop.cpp) checks them against the exact f64 Sphere::hit
+// (sphere.rs:77-108) on random and adversarial rays, and
+// tests/test_walk_filters_gpu.py runs the same cases through the device build
+// (rt_walk_selftest).
 //
 // Reference algorithm (sphere.rs:77-96): oc = c - o, a = |d|^2, h = d.oc,
 // cc = |oc|^2 - r^2, disc = h^2 - a cc; hit at the near root (h - sqrt(disc))/a

@@ -6,7 +6,9 @@ script, camera and render seed; prints per-channel RMSE of the linear f32
 frames, the largest absolute difference, and the fractions of pixels that are
 bit-equal / within 1e-5 relative.  The GPU parity tests check rows of the
 full-size configs; this checks every pixel of a whole frame.
-  python scripts/full_frame_parity.py c2 [spp]"""
+c1 is BASELINE configs[0], which bench.py does not time: the book-1 scene at
+400x225, 100 spp (scenes.random_spheres).
+  python scripts/full_frame_parity.py c1|c2|... [spp]"""
 import ctypes
 import importlib
 import json
@@ -30,7 +32,8 @@ pkg = importlib.import_module("raytracer-2025_amd")
 
 def main():
     wl = sys.argv[1] if len(sys.argv) > 1 else "c2"
-    spp = int(sys.argv[2]) if len(sys.argv) > 2 else bench.WORKLOADS[wl][1]
+    workloads = dict(bench.WORKLOADS, c1=(400, 100))
+    spp = int(sys.argv[2]) if len(sys.argv) > 2 else workloads[wl][1]
     threads, _ = bench.usable_cpus()
     so = os.path.join(ROOT, "oracle", "_build", "liboracle_fast.so")  # the timed build: the same bits as liboracle.so (tests/test_oracle_golden.py), faster
     if not os.path.exists(so):
@@ -39,7 +42,11 @@ def main():
     out = {}
     for name, api in (("gpu", pkg.load()), ("oracle", capi.Api(ctypes.CDLL(so), "orc_", capi.ORACLE_EXTRAS))):
         s = rt.Scene(api)
-        world, lights, cam, desc = bench.build_workload(scenes, s, wl, bench.WORKLOADS[wl][0], spp)
+        if wl == "c1":
+            world, lights, cam = scenes.random_spheres(s, workloads[wl][0], spp)
+            desc = "C1: book-1 random spheres, reference CPU size"
+        else:
+            world, lights, cam, desc = bench.build_workload(scenes, s, wl, workloads[wl][0], spp)
         t0 = time.perf_counter()
         if name == "gpu":
             lin, _, st = cam.render(world, lights, seed=1, want_srgb=False)

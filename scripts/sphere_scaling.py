@@ -4,8 +4,9 @@ worlds -- the ground sphere plus N small spheres drawn with the R28 recipe
  over a square of cells around the book-1 camera's view, three big
 spheres -- at 1920x1080, --spp (default 64), depth 50.  Prints per N the
 kernel tier the launcher picked, the 4-wide node count and the path-kernel
-Msamples/s: where the basic tier's LDS node copy ends and the mesh tier
-takes over.
+Msamples/s (the best of SCALING_REPS timed renders, default 3, all of them
+listed with their spread): where the basic tier's LDS node copy ends and the
+mesh tier takes over.
   python scripts/sphere_scaling.py [spp] [N ...]"""
 import ctypes
 import importlib
@@ -69,11 +70,13 @@ def main():
         info = capi.RtWorldInfo()
         api.check(api.world_info_get(s.s, w.h, -1, cam.background.h, 0, ctypes.byref(info)))
         cam.render(w, None, seed=1, want_srgb=False)  # warm-up + upload
-        best = None
-        for _ in range(3):
+        ms = []
+        for _ in range(int(os.environ.get("SCALING_REPS", "3"))):
             _, _, st = cam.render(w, None, seed=1, want_srgb=False)
-            best = st.kernel_ms if best is None else min(best, st.kernel_ms)
+            ms.append(round(st.kernel_ms, 3))
+        best = min(ms)
         rec = {"spheres": n + 4, "tier": info.kernel_tier, "bvh4_nodes": info.bvh_nodes, "kernel_ms": round(best, 3),
+               "kernel_ms_all": ms, "spread": round((max(ms) - best) / best, 4),
                "msamples_per_s": round(cam.traced_samples() / (best * 1e-3) / 1e6, 1)}
         print(json.dumps(rec), flush=True)
         out.append(rec)

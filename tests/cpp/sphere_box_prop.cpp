@@ -1,0 +1,171 @@
+// TEST HARNESS: property test of the basic tier's boxed sphere children.  The
+// 4-wide flatten (rth::bvh4_convert) gives a sphere child an f32 box
+// (rt_slab.h sphere_box_f: c -+ r widened by the f64 test's slop for origins
+// within the world's extent, at least 2^-16 r, rounded outward), and the walk
+// queues the sphere for its exact f64 test only when the conservative f32 slab
+// test (raytracer-2025_amd/csrc/rt_slab.h slab_f) admits that box.  So, for
+// every (ray, sphere, bound c) triple:
+//   the exact f64 Sphere::hit (sphere_exact.cpp, sphere.rs:77-108) returns a
+//   root in [1e-8, c]   =>   slab_f(box, make_rayf(ray), f32_down(1e-8), c_f)
+// with c_f made from c as the kernel's Closest makes it.  No violation is
+// allowed: a culled sphere the exact test would have hit changes the image.
+// The world's extent given to sphere_box_f is the least the flatten could
+// pass for the case: the larger of |c - o| and the sphere's own box diagonal.
+// Cases: random, and adversarial -- tangent rays, origins on the surface (the
+// poles, where the sphere touches a face of its box, included) and a hair off
+// it, origins inside, rays that run in a face plane of the box, direction
+// components of +-0, 1e-40 (subnormal in f32) and 1e-300 (zero in f32),
+// integer centres with r = 0.5 or 1 (c +- r exact in f32: no rounding slack),
+// r = 1000 with the origin on it, r = 1e-3, worlds offset by 4096; and, outside
+// the 2^-16 r term's reach, origins up to 3e6 radii away (aimed at the rim, or
+// in a face plane with the pole ahead) and r = 0.
+// Prints "cases exact_hits box_misses violations" and exits 1 on any violation.
+// sphere_box_prop [n [seed]]
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+
+#include "../../raytracer-2025_amd/csrc/rt_slab.h"
+
+extern "C" double exact_sphere_t(const double c[3], double r, const double o[3], const double d[3], double tmin,
+                                 double tmax);
+
+// as rt_scene.cpp's round_down / round_up: the f32 not above / not below x
+static float round_down_f(double x) {
+    float f = (float)x;
+    if ((double)f > x) f = std::nextafter(f, -INFINITY);
+    return f;
+}
+static float round_up_f(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = std::nextafter(f, INFINITY);
+    return f;
+}
+// as rt_kernel.hip's Closest::set
+static float closest_cf(double t) {
+    const float f = (float)t;
+    return fmaf(fabsf(f), 1.1920928955078125e-07f, f);
+}
+
+int main(int argc, char** argv) {
+    const long n = argc > 1 ? std::atol(argv[1]) : 1000000;
+    std::mt19937_64 rng(argc > 2 ? std::atoll(argv[2]) : 2025);
+    std::uniform_real_distribution<double> U(0.0, 1.0);
+    auto unit = [&](double v[3]) {
+        double z = 1 - 2 * U(rng), r = std::sqrt(std::fmax(0.0, 1 - z * z)), p = 2 * M_PI * U(rng);
+        v[0] = r * std::cos(p);
+        v[1] = r * std::sin(p);
+        v[2] = z;
+    };
+    auto pick = [&](int k) { return (int)(U(rng) * k); };
+    const float tmin_f = rtk::f32_down(1e-8);
+    long hits = 0, box_miss = 0, bad = 0;
+    for (long i = 0; i < n; ++i) {
+        // sphere: book-1 ground / small / big, far away, tiny, general, and
+        // the exactly representable ones (integer centre, r = 0.5 or 1; r = 1e-3
+        // at an integer centre); every fourth world offset by 4096 in x and z
+        double c[3], r;
+        const int kind = pick(9);
+        if (kind == 0) { c[0] = 0; c[1] = -1000; c[2] = 0; r = 1000; }
+        else if (kind == 1) { c[0] = -11 + 22 * U(rng); c[1] = 0.2; c[2] = -11 + 22 * U(rng); r = 0.2; }
+        else if (kind == 2) { c[0] = 4 * pick(3) - 4; c[1] = 1; c[2] = 0; r = 1; }
+        else if (kind == 3) { c[0] = 1e4 * (U(rng) - 0.5); c[1] = 1e4 * (U(rng) - 0.5); c[2] = 1e3 * U(rng); r = 1e-3 + U(rng); }
+        else if (kind == 4) { c[0] = U(rng); c[1] = U(rng); c[2] = U(rng); r = 1e-3 * (1 + U(rng)); }
+        else if (kind == 5) { c[0] = 100 * (U(rng) - 0.5); c[1] = 50 * U(rng); c[2] = 100 * (U(rng) - 0.5); r = 50 * U(rng) + 0.01; }
+        else if (kind == 6) { for (int k = 0; k < 3; ++k) c[k] = pick(9) - 4; r = pick(2) ? 0.5 : 1.0; }
+        else if (kind == 7) { for (int k = 0; k < 3; ++k) c[k] = pick(9) - 4; r = 1e-3; }
+        else { for (int k = 0; k < 3; ++k) c[k] = pick(2) ? pick(9) - 4 : 8 * (U(rng) - 0.5); r = 0.0; }
+        const bool offset = pick(4) == 0;
+        if (offset) { c[0] += 4096; c[2] += 4096; }
+        // origin: on the surface, a hair off it, at the book-1 camera, anywhere,
+        // inside, on the surface at a pole (on a face of the box), on a face
+        // plane of the box away from the pole, or far away (1e2 to 3e6 radii)
+        double o[3], d[3], nrm[3];
+        unit(nrm);
+        const int ok = pick(8);
+        const bool pole = ok == 5 || ok == 6;
+        if (pole) {
+            const int ax = pick(3);
+            nrm[0] = nrm[1] = nrm[2] = 0.0;
+            nrm[ax] = pick(2) ? 1.0 : -1.0;
+        }
+        const double lift = ok == 1 ? (U(rng) - 0.5) * 1e-6 * r : 0.0;
+        if (ok <= 1 || pole) for (int k = 0; k < 3; ++k) o[k] = c[k] + (r + lift) * nrm[k];
+        else if (ok == 2) { o[0] = 13 + (offset ? 4096 : 0); o[1] = 2; o[2] = 3 + (offset ? 4096 : 0); }
+        else if (ok == 4) {  // inside: anywhere from the center to a hair below the surface
+            const double f = U(rng) < 0.5 ? U(rng) : 1.0 - std::exp(std::log(1e-12) + U(rng) * std::log(1e10));
+            for (int k = 0; k < 3; ++k) o[k] = c[k] + f * r * nrm[k];
+        }
+        else if (ok == 7) {
+            const double f = std::exp(std::log(1e2) + U(rng) * std::log(3e4));
+            for (int k = 0; k < 3; ++k) o[k] = c[k] + f * (r > 0 ? r : 1.0) * nrm[k];
+        }
+        else for (int k = 0; k < 3; ++k) o[k] = c[k] + (U(rng) - 0.5) * 40 * (r + 1);
+        // direction: random, tangent at the origin's surface point (for a
+        // pole: in the box's face plane, the normal component exactly zero or
+        // a hair), or aimed at the rim as seen from o
+        const int dk = pick(3);
+        unit(d);
+        if (dk == 1 && (ok <= 1 || pole)) {
+            const double dn = d[0] * nrm[0] + d[1] * nrm[1] + d[2] * nrm[2];
+            for (int k = 0; k < 3; ++k) d[k] -= dn * nrm[k];
+            if (pole) {
+                static const double hair[4] = {0.0, 1e-40, 1e-300, 1e-17};
+                const double e = hair[pick(4)] * (pick(2) ? 1.0 : -1.0);
+                for (int k = 0; k < 3; ++k)
+                    if (nrm[k] != 0.0) d[k] = e;
+            } else {
+                for (int k = 0; k < 3; ++k) d[k] += (U(rng) - 0.5) * 1e-7 * nrm[k];
+            }
+            if (ok == 6) {  // slide the origin back along the ray: the pole is ahead, at t = s / |d|
+                const double s = (pick(2) ? std::exp(std::log(1e-6) + U(rng) * std::log(1e8))
+                                          : std::exp(std::log(1e2) + U(rng) * std::log(3e4))) * r;
+                for (int k = 0; k < 3; ++k) o[k] -= s * d[k];
+            }
+        } else if (dk == 2) {
+            double t[3], p[3];
+            unit(t);
+            for (int k = 0; k < 3; ++k) p[k] = c[k] + r * (1 + (U(rng) - 0.5) * 1e-6) * t[k];
+            for (int k = 0; k < 3; ++k) d[k] = p[k] - o[k];
+        }
+        const double len = std::exp(std::log(1e-2) + U(rng) * std::log(1e4));  // |d| in [0.01, 100]
+        for (int k = 0; k < 3; ++k) d[k] *= len;
+        const int zk = pick(10);
+        if (zk < 3) {
+            static const double tiny[3] = {0.0, 1e-40, 1e-300};
+            d[pick(3)] = pick(2) ? -tiny[zk] : tiny[zk];
+        }
+        // the walk's bound: none, random, or right at the exact root
+        const double t_any = exact_sphere_t(c, r, o, d, 1e-8, INFINITY);
+        double cb = INFINITY;
+        const int bk = pick(4);
+        if (bk == 1) cb = std::exp(std::log(1e-6) + U(rng) * std::log(1e10));
+        else if (bk == 2 && t_any >= 0) cb = t_any;
+        else if (bk == 3 && t_any >= 0) cb = t_any * (1.0 + U(rng) * 1e-5);
+        const float cf = std::isinf(cb) ? INFINITY : closest_cf(cb);
+        const double tx = exact_sphere_t(c, r, o, d, 1e-8, cb);
+
+        float lo[3], hi[3];
+        const double s4[4] = {c[0], c[1], c[2], r};
+        const double oc = std::sqrt((c[0] - o[0]) * (c[0] - o[0]) + (c[1] - o[1]) * (c[1] - o[1]) +
+                                    (c[2] - o[2]) * (c[2] - o[2]));
+        rtk::sphere_box_f(s4, std::fmax(oc, 2 * std::sqrt(3.0) * r), lo, hi);  // the box as the flatten makes it
+        for (int k = 0; k < 3; ++k)     // which holds the rounded c -+ r
+            if (!(lo[k] <= round_down_f(c[k] - r) && hi[k] >= round_up_f(c[k] + r))) ++bad;
+        const rtk::RayF rf = rtk::make_rayf(o, d);
+        float e;
+        const bool keep = rtk::slab_f(lo, hi, rf, tmin_f, cf, e);
+        hits += tx >= 0;
+        box_miss += !keep;
+        if (tx >= 0 && !keep) {
+            if (bad < 10)
+                std::printf("VIOLATION kind %d offset %d origin %d dir %d bound %d: c=(%.17g %.17g %.17g) r=%.17g "
+                            "o=(%.17g %.17g %.17g) d=(%.17g %.17g %.17g) exact t=%.17g c=%.17g cf=%.9g\n",
+                            kind, (int)offset, ok, dk, bk, c[0], c[1], c[2], r, o[0], o[1], o[2], d[0], d[1], d[2], tx, cb, cf);
+            ++bad;
+        }
+    }
+    std::printf("%ld %ld %ld %ld\n", n, hits, box_miss, bad);
+    return bad ? 1 : 0;
+}
