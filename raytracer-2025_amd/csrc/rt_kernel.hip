@@ -23,6 +23,7 @@
 #include "rt_kernel.h"
 #include "rt_math.h"
 #include "rt_slab.h"
+#include "rt_sort4.h"
 #include "rt_sphere_filter.h"
 #include "rt_plan.h"
 
@@ -545,13 +546,18 @@ struct StackB4 {
     }
     // The 4-wide basic tier's walk keeps its refs as "words" (bword): a
     // box child's 16-bit stack code in the upper half -- push is one byte
-    // permute with the entry distance, pop one mask
+    // permute with the entry distance, pop one mask.  The visit pushes its
+    // sorted children as sort words (rt_sort4.h: the same halves the other
+    // way round), one 16-bit rotate each.
     __device__ __forceinline__ void push_w(uint32_t sp, uint32_t word, float t) {
-        base[sp * BLK] = __builtin_amdgcn_perm(word, __float_as_uint(t), 0x07060302u);
+        base[sp * BLK] = stack4_word(word, t);
+    }
+    __device__ __forceinline__ void push_sorted(uint32_t sp, uint32_t sort_word) {
+        base[sp * BLK] = sort4_stack_word(sort_word);
     }
     __device__ __forceinline__ uint2 at_w(uint32_t sp) const {
         const uint32_t e = base[sp * BLK];
-        return make_uint2(e & 0xffff0000u, e << 16);
+        return make_uint2(stack4_walk_word(e), __float_as_uint(stack4_dist(e)));
     }
 };
 // Basic-tier walk words (the 4-wide walk's cur, stack entries and the ref
@@ -1302,6 +1308,10 @@ __device__ __forceinline__ void media_phase(const SceneView& S, const WR& wrr, T
 // the box admits more rays -- 1.88 exact tests a ray on C2 instead of 1.49 --
 // and gives the walk no early bound -- 5.32 node visits a ray instead of 5.01
 // -- yet C2 is 3.5 % faster: profiles/r07/ab_boxed_spheres_c2_128spp.json.)
+// The sort runs on packed words (rt_sort4.h): the upper half of the entry
+// distance above the child's 16-bit ref code, min / max per exchange, and a
+// 16-bit rotate makes the stack entry -- where (f32 key, ref) pairs took a
+// compare and four selects per exchange and a byte permute per push.
 struct Node4Rows {
     float4 lx, ly, lz, hx, hy, hz, rq;
 };
@@ -1327,52 +1337,49 @@ __device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4R
     const float LX[4] = {lx.x, lx.y, lx.z, lx.w}, LY[4] = {ly.x, ly.y, ly.z, ly.w}, LZ[4] = {lz.x, lz.y, lz.z, lz.w};
     const float HX[4] = {hx.x, hx.y, hx.z, hx.w}, HY[4] = {hy.x, hy.y, hy.z, hy.w}, HZ[4] = {hz.x, hz.y, hz.z, hz.w};
     const uint32_t R[4] = {__float_as_uint(rq.x), __float_as_uint(rq.y), __float_as_uint(rq.z), __float_as_uint(rq.w)};
-    constexpr float INF = __builtin_huge_valf();
-    float key[4];
-    uint32_t ref[4];
+    uint32_t w[4];
     // per slot, one slab test when some lane has a child there: a sphere
     // child's row holds its own box (rth::bvh4_convert), and a hit queues it
-    // for the exact test where a box child's hit gets its sort key.  The
-    // flatten puts a node's empty slots last.
+    // for the exact test where a box child's hit gets its sort word
+    // (rt_sort4.h: the upper half of the entry distance above the ref code).
+    // The queue takes the walk word's low half as it stands -- trace4_step
+    // masks the sphere flag off where it reads the index.  The flatten puts
+    // a node's empty slots last.
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const bool sph = (uint16_t)R[i] != 0, box = R[i] > 0xffffu;
-        key[i] = INF;
-        ref[i] = R[i];
-        if (__ballot(sph || box)) {
+        // a child is a box (word > 0xffff, low half zero) or a sphere (upper
+        // half zero): the sphere flag comes from the two compares the slot
+        // needs anyway, as a mask operation
+        const bool any = R[i] != 0u, box = R[i] > 0xffffu, sph = any && !box;
+        w[i] = SORT4_NONE;
+        if (__ballot(any)) {
             const float lo[3] = {LX[i], LY[i], LZ[i]}, hi[3] = {HX[i], HY[i], HZ[i]};
             float e;
             const bool h = slab_f(lo, hi, rf, tmin_f, c_f, e);
-            if (h && sph) {
-                pq[pn * RT_BLOCK_BASIC] = (uint16_t)(R[i] & 0x7fffu);
-                ++pn;
-            }
-            key[i] = h && box ? e : INF;
+            // The queue store is unconditional and only the count is not: a
+            // lane that queues nothing writes above its queue's top, into an
+            // entry nothing reads before the next push overwrites it.  That
+            // entry exists: a lane visits with pn <= RT_PEND_CAP - 4
+            // (trace4_step's ROOM) and slot i has added at most i, so the
+            // index is at most RT_PEND_CAP - 1.  An address, a store and a
+            // select-and-add where the store under its own lane mask took an
+            // instruction and two mask operations more (C2 -1.0 %,
+            // profiles/r08/ab_packed_sort_variants_c2_128spp.json).
+            pq[pn * RT_BLOCK_BASIC] = (uint16_t)R[i];
+            pn += h && sph ? 1u : 0u;
+            w[i] = sort4_word(h && box, e, R[i]);
         }
     }
     // no lane of the wave hit a box child (nodes of spheres only, or every
     // box missed): nothing to sort or push (C2 -0.65 %, A/B at 128 spp, 5
     // reps, RMSE 0; a two-slot network when no lane has a box in slots 0 and
     // 1 was +1.9 %)
-    if (!__ballot(fminf(fminf(key[0], key[1]), fminf(key[2], key[3])) < INF)) return 0u;
-    auto cs = [&](int a, int b) {  // compare-exchange: key[a] <= key[b] afterwards
-        const bool sw = key[b] < key[a];
-        const float ka = key[a], kb = key[b];
-        const uint32_t ra = ref[a], rb = ref[b];
-        key[a] = sw ? kb : ka;
-        key[b] = sw ? ka : kb;
-        ref[a] = sw ? rb : ra;
-        ref[b] = sw ? ra : rb;
-    };
-    cs(0, 1);
-    cs(2, 3);
-    cs(0, 2);
-    cs(1, 3);
-    cs(1, 2);
-    if (key[3] < INF) stk.push_w(sp++, ref[3], key[3]);
-    if (key[2] < INF) stk.push_w(sp++, ref[2], key[2]);
-    if (key[1] < INF) stk.push_w(sp++, ref[1], key[1]);
-    return key[0] < INF ? ref[0] : 0u;
+    if (!__ballot(sort4_least(w) != SORT4_NONE)) return 0u;
+    sort4(w);
+    if (w[3] != SORT4_NONE) stk.push_sorted(sp++, w[3]);
+    if (w[2] != SORT4_NONE) stk.push_sorted(sp++, w[2]);
+    if (w[1] != SORT4_NONE) stk.push_sorted(sp++, w[1]);
+    return w[0] != SORT4_NONE ? sort4_walk_word(w[0]) : 0u;
 }
 
 // One visit of a DNode4 whose children all carry boxes (mesh tier): four slab
@@ -1482,7 +1489,7 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
     // entry 0, cache-hot) so that no branch stands between them and their
     // waits: the sphere test then waits for its own load only
     const uint32_t top = pn > 0 ? pn - 1 : 0;
-    const uint32_t sidx = pq[top * RT_BLOCK_BASIC];
+    const uint32_t sidx = pq[top * RT_BLOCK_BASIC] & 0x7fffu;  // queued with the walk word's sphere flag
     pn -= round ? 1u : 0u;
     const double4 s4 = S.spheres[round ? sidx : 0u];
     uint32_t cur = REF_NONE;
@@ -1515,7 +1522,7 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
                 T.cur = bword(S, child);
             }
         } else {  // a sphere element of a list: queued for its exact test
-            pq[pn * RT_BLOCK_BASIC] = (uint16_t)(cur & 0x7fffu);
+            pq[pn * RT_BLOCK_BASIC] = (uint16_t)cur;
             ++pn;
         }
     }

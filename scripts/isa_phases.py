@@ -27,12 +27,26 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 KERNEL = "_ZN3rtk14rt_path_kernelILi0ELb0EEEvPKNS_7KParamsE"
 
 
+RESOURCES = {}  # of the last asm() call: kernel -> {vgprs, scratch_bytes_per_lane, waves_per_simd}
+
+
 def asm(extra):
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-o", out, SRC], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-Rpass-analysis=kernel-resource-usage", "-o", out,
+                            SRC], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
         text = open(out).read()
+    RESOURCES.clear()
+    cur = None
+    for ln in r.stderr.splitlines():  # the compiler's resource remarks, a block per kernel
+        m = re.search(r"remark:\s+(Function Name|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", ln)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            cur = RESOURCES.setdefault(m.group(2), {})
+        elif cur is not None:
+            cur[{"VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
+                 "Occupancy [waves/SIMD]": "waves_per_simd"}[m.group(1)]] = int(m.group(2))
     start = text.index(KERNEL + ":")
     end = text.index(".Lfunc_end", start)
     return text[start:end].splitlines()
@@ -85,7 +99,10 @@ def count(lines):
 def main():
     marked, total_m = count(asm(["-DRT_ISA_MARKS"]))
     _, total_p = count(asm([]))
+    wide = KERNEL.replace("Lb0", "Lb1")  # rt_path_kernel<0, true>: trees past the batch variant's LDS node copy
     out = {
+        "resources_product_build": {"rt_path_kernel<0, false>": dict(RESOURCES.get(KERNEL, {})),
+                                    "rt_path_kernel<0, true>": dict(RESOURCES.get(wide, {}))},
         "kernel": "rt_path_kernel<0, false> (basic tier, 56-lane shading batches: C1 / C2)",
         "method": "static instruction counts in layout order after each RT_ISA_MARK comment (-DRT_ISA_MARKS); "
                   "a phase's count is its code once, not how often it runs",
