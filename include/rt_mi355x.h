@@ -226,7 +226,7 @@ int32_t rt_render(rt_scene* s, int32_t world, int32_t lights, const rt_camera* c
 /* What rt_render would upload for (world, lights): host-only, no device needed. */
 typedef struct rt_world_info {
     uint64_t device_bytes;    /* size of the flattened world blob */
-    uint32_t bvh_nodes;       /* two-box BVH nodes */
+    uint32_t bvh_nodes;       /* 4-wide BVH nodes the kernel walks */
     uint32_t primitives;      /* spheres + moving spheres + quads + triangles */
     uint32_t bvh_leaves;      /* objects under BVHs */
     uint32_t stack_need;      /* traversal-stack entries one lane needs */

@@ -96,15 +96,8 @@ struct rtk_frame_desc {
     void* ev_stop;
 };
 
-extern "C" int rtk_tier_for(uint32_t features, uint32_t stack_need);
+extern "C" int rtk_tier_for(uint32_t features);
 extern "C" uint32_t rtk_stack_entries(int tier);
-// 1 if the basic tier's kernel walks 4-wide BVH nodes (rth::bvh4_basic)
-extern "C" int rtk_basic_bvh4(void);
-// 1 if the mesh tier's kernel walks 4-wide BVH nodes with every child boxed
-extern "C" int rtk_mesh_bvh4(void);
-// 1 if the kernel runs the f32 quad / triangle pre-test (rt_planar_filter.h)
-extern "C" int rtk_planar_filter(void);
-extern "C" int rtk_full_bvh4(void);
 extern "C" hipError_t rtk_launch_frame(const rtk::SceneView* view, const rtk_frame_desc* fd, uint32_t* queue,
                                        double* partial, unsigned long long* stats, float* out, uint8_t* srgb,
                                        int toon, hipStream_t stream, int tier, int grid, void* params_dev,

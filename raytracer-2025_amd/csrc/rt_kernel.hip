@@ -29,24 +29,14 @@
 
 namespace rtk {
 
-// Basic tier: 4-wide BVH nodes (rth::bvh4_convert), sphere children through
-// the slab test of their own f32 box (rt_slab.h sphere_box_f) into a per-lane
-// LDS queue of exact tests (visit4_rows); 0 = two-box nodes with inline f64
-// sphere tests.  (rt_sphere_filter.h is no longer called by the path kernels:
-// only rt_walk_selftest runs it.)
-#ifndef RT_BVH4
-#define RT_BVH4 1
-#endif
+// Every BVH tier walks 4-wide nodes (rth::bvh4_convert).  Basic tier: sphere
+// children go through the slab test of their own f32 box (rt_slab.h
+// sphere_box_f) into a per-lane LDS queue of exact tests (visit4_rows).  Mesh
+// and full tiers: every child boxed (visit4_boxes), for the walk and the
+// medium boundary walks.  (rt_sphere_filter.h is not called by the path
+// kernels: only rt_walk_selftest runs it.)
 #ifndef RT_PEND_CAP
 #define RT_PEND_CAP 8  // queued sphere tests per lane (LDS, 2 B each: sphere index < 65536)
-#endif
-// Mesh tier: 4-wide BVH nodes with every child boxed (visit4_boxes).
-#ifndef RT_MESH_BVH4
-#define RT_MESH_BVH4 1
-#endif
-// Full tier: the same boxed 4-wide nodes, for the walk and the medium boundary walks.
-#ifndef RT_FULL_BVH4
-#define RT_FULL_BVH4 1
 #endif
 
 // Diagnostic build (-DRT_DIAG, librt_mi355x_diag.so only): per-wave cycle
@@ -216,9 +206,6 @@ __device__ __forceinline__ uint32_t udiv_inv(uint32_t n, double inv) { return (u
 // ------------------------------------------------------------------ textures
 // texture.rs: SolidColor 33-36, CheckerTexture 60-73, ImageTexture 165-174,
 // NoiseTexture 191-196 (+ perlin.rs), book-1 sky.
-#ifndef RT_PERLIN_LDS
-#define RT_PERLIN_LDS 1
-#endif
 // Full tiers: the block's LDS copy of the world's first Perlin table (9 KiB,
 // copied at launch), read by NoiseTexture instead of global memory: the
 // marble's 7 octaves are 14 dependent table reads per shade, and a shading
@@ -289,12 +276,6 @@ __device__ __forceinline__ double tex_alpha(const SceneView& S, int tid, double 
     return (double)px[3];
 }
 
-#ifndef RT_BG_PARAMS
-// 1: the basic and mesh tiers' miss under a sky gradient reads its colours
-// from the launch parameters (SceneView::bg_c0 / bg_c1); 0: from the texture
-// table (A/B only)
-#define RT_BG_PARAMS 1
-#endif
 // the sky gradient (rt_tex_sky_gradient, include/rt_mi355x.h) at the unit direction's y
 __device__ __forceinline__ D3 sky_value(const double* c0, const double* c1, double py) {
     const double a = 0.5 * (py + 1.0);
@@ -423,27 +404,6 @@ __device__ __forceinline__ bool planar_t(const DPlanar& P, bool tri, const Ray& 
                       d3(P.f[10], P.f[11], P.f[12]), d3(P.f[13], P.f[14], P.f[15]), tri, r, tmin, tmax, t);
 }
 
-#ifndef RT_PLANAR_FILTER
-// 1: quads / triangles take the f32 pre-test (rt_planar_filter.h) before
-// planar_t.  Measured slower (A/B at 128 spp, min of 4: C4 +13 %, C5 +5 %,
-// C3 +2 %): a triangle reached through a hit box is rarely ruled out, and a
-// flat-tier quad's f32 test costs about what the f64 one does.  Kept as an
-// option with its CPU property test (tests/test_planar_filter_cpu.py).
-#define RT_PLANAR_FILTER 0
-#endif
-// planar_t behind the conservative f32 pre-test: the f64 record is read and
-// tested only when the f32 test cannot rule the primitive out.  The
-// pre-test's "behind the origin" rejection needs tmin >= 0 (a medium
-// boundary walk starts at -inf).
-__device__ __forceinline__ bool planar_t_filtered(const SceneView& S, uint32_t idx, bool tri, const Ray& r,
-                                                  double tmin, double tmax, float tmax_f, double& t) {
-    if constexpr (RT_PLANAR_FILTER) {
-        const double o[3] = {r.o.x, r.o.y, r.o.z}, d[3] = {r.d.x, r.d.y, r.d.z};
-        if (tmin >= 0.0 && planar_reject(S.planars_f[idx], make_prayf(o, d), tmax_f, tri)) return false;
-    }
-    return planar_t(S.planars[idx], tri, r, tmin, tmax, t);
-}
-
 // Quaternion::rotate_vector (quaternion.rs:72-82): (q * (0, v)) * conj(q)
 // with Mul (quaternion.rs:94-103) term by term in the reference's order; the
 // products with qv.w = 0 are exact zeros, so a + 0*b is a and those terms
@@ -502,10 +462,10 @@ struct HitInfo {
 // The per-lane traversal stack: entry k of lane l at stk[k * RT_BLOCK] (the
 // pointer is already offset by the lane), {ref, entry distance as f32 rounded
 // down} -- one ds_write_b64 / ds_read_b64 per push / pop, 64 distinct banks
-// per half-wave.  With OVF, entries k >= CAP (deep triangle BVHs) live in the
-// lane's column of a global overflow buffer, [k - CAP][lane of the grid], so
-// the LDS part stays small enough for 4 blocks per CU.
-template <uint32_t CAP, bool OVF, uint32_t BLK>
+// per half-wave.  Entries k >= CAP (deep triangle BVHs) live in the lane's
+// column of a global overflow buffer, [k - CAP][lane of the grid], so the LDS
+// part stays small enough for 4 blocks per CU.
+template <uint32_t CAP>
 struct StackT {
     RT_LDS uint2* base;  // explicitly LDS: a select against ovf must not become a flat pointer
     RT_GLOBAL uint2* ovf;
@@ -515,18 +475,18 @@ struct StackT {
     // two accesses into one through a phi of flat pointers (which also hit a
     // gfx950 code-generation error on an LDS-to-flat cast in the flat tier).
     __device__ __forceinline__ void push(uint32_t sp, uint32_t ref, float t) {
-        if (OVF && sp >= CAP)
+        if (sp >= CAP)
             reinterpret_cast<RT_GLOBAL unsigned long long*>(ovf)[(sp - CAP) * stride] =
                 ((unsigned long long)__float_as_uint(t) << 32) | ref;
         else
-            base[sp * BLK] = make_uint2(ref, __float_as_uint(t));
+            base[sp * RT_BLOCK] = make_uint2(ref, __float_as_uint(t));
     }
     __device__ __forceinline__ uint2 at(uint32_t sp) const {
-        if (OVF && sp >= CAP) {
+        if (sp >= CAP) {
             const unsigned long long v = reinterpret_cast<const RT_GLOBAL unsigned long long*>(ovf)[(sp - CAP) * stride];
             return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
         }
-        return base[sp * BLK];
+        return base[sp * RT_BLOCK];
     }
 };
 // Basic tier: 4-B entries -- a list flag and a 15-bit node / list
@@ -536,15 +496,7 @@ struct StackT {
 template <uint32_t CAP, uint32_t BLK>
 struct StackB4 {
     RT_LDS uint32_t* base;
-    __device__ __forceinline__ void push(uint32_t sp, uint32_t ref, float t) {
-        const uint32_t r16 = (ref_kind(ref) == K_LIST ? 0x8000u : 0u) | (ref_index(ref) & 0x7fffu);
-        base[sp * BLK] = (r16 << 16) | (__float_as_uint(t) >> 16);
-    }
-    __device__ __forceinline__ uint2 at(uint32_t sp) const {
-        const uint32_t e = base[sp * BLK], r16 = e >> 16;
-        return make_uint2(make_ref((r16 & 0x8000u) ? K_LIST : K_BVH, r16 & 0x7fffu), e << 16);
-    }
-    // The 4-wide basic tier's walk keeps its refs as "words" (bword): a
+    // The basic tier's walk keeps its refs as "words" (bword): a
     // box child's 16-bit stack code in the upper half -- push is one byte
     // permute with the entry distance, pop one mask.  The visit pushes its
     // sorted children as sort words (rt_sort4.h: the same halves the other
@@ -580,13 +532,13 @@ __device__ __forceinline__ uint32_t pop_w(const Stack& stk, uint32_t& sp, float 
     }
     return 0u;
 }
-template <int TIER, bool B4 = TIER == TIER_BASIC>
-struct StackSel {
-    using type = StackT<lds_stack_entries(TIER), TIER != TIER_BASIC, TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK>;
-};
 template <int TIER>
-struct StackSel<TIER, true> {
-    using type = StackB4<lds_stack_entries(TIER), RT_BLOCK_BASIC>;
+struct StackSel {
+    using type = StackT<lds_stack_entries(TIER)>;
+};
+template <>
+struct StackSel<TIER_BASIC> {
+    using type = StackB4<lds_stack_entries(TIER_BASIC), RT_BLOCK_BASIC>;
 };
 template <int TIER>
 using StackFor = typename StackSel<TIER>::type;
@@ -611,51 +563,6 @@ struct Closest {
     }
 };
 
-// One BVH node visit (one 80-B record): a sphere child is intersected right
-// here from the data in its slot (sphere.rs:77-108); other children get the
-// f32 slab test, and the hit ones are walked near-first with the farther one
-// pushed with its entry distance.
-template <class Stack, class OnHit>
-__device__ __forceinline__ uint32_t visit_node(const SceneView& S, uint32_t idx, const Ray& r, const RayF& rf,
-                                               double a, double inva, double tmin, float tmin_f, Closest& cl,
-                                               Stack& stk, uint32_t& sp, OnHit&& on_hit) {
-    const RT_GLOBAL float4* np = reinterpret_cast<const RT_GLOBAL float4*>(S.nodes + idx);
-    const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3], q4 = np[4];
-    const uint32_t c0 = __float_as_uint(q4.x), c1 = __float_as_uint(q4.y);
-    bool h0 = false, h1 = false;
-    float e0 = 0.0f, e1 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t ch = k ? c1 : c0;
-        const float4 qa = k ? q2 : q0, qb = k ? q3 : q1;
-        bool& hk = k ? h1 : h0;
-        float& ek = k ? e1 : e0;
-        if (ch == REF_NONE) continue;
-        if (ref_kind(ch) == K_SPHERE) {
-            const double cx = __hiloint2double(__float_as_int(qa.y), __float_as_int(qa.x));
-            const double cy = __hiloint2double(__float_as_int(qa.w), __float_as_int(qa.z));
-            const double cz = __hiloint2double(__float_as_int(qb.y), __float_as_int(qb.x));
-            const double rr = __hiloint2double(__float_as_int(qb.w), __float_as_int(qb.z));
-            double t;
-            if (sphere_t_inv(d3(cx, cy, cz), rr, r, a, inva, tmin, cl.c, t)) {
-                cl.set(t);
-                on_hit(ch, t);
-            }
-        } else {
-            const float lo[3] = {qa.x, qa.y, qa.z}, hi[3] = {qa.w, qb.x, qb.y};
-            hk = slab_f(lo, hi, rf, tmin_f, cl.c_f, ek);
-        }
-    }
-    h0 = h0 && e0 <= cl.c_f;
-    h1 = h1 && e1 <= cl.c_f;
-    if (h0 && h1) {
-        const bool first0 = e0 <= e1;
-        stk.push(sp++, first0 ? c1 : c0, first0 ? e1 : e0);
-        return first0 ? c0 : c1;
-    }
-    return h0 ? c0 : (h1 ? c1 : REF_NONE);
-}
-
 // Pops until an entry whose box can still hold a hit closer than c.
 template <class Stack>
 __device__ __forceinline__ uint32_t pop(const Stack& stk, uint32_t& sp, uint32_t sp0, float c_f) {
@@ -678,7 +585,7 @@ template <int TIER>
 constexpr bool flat_boxes() { return TIER == TIER_FULL_FLAT; }
 template <int TIER>
 constexpr bool unified_load() {
-    return (TIER == TIER_MESH && RT_MESH_BVH4) || (tier_full_bvh(TIER) && RT_FULL_BVH4);
+    return TIER == TIER_MESH || tier_full_bvh(TIER);
 }
 // the two doubles of a float4 read from a double record
 __device__ __forceinline__ double f4_lo(float4 q) { return __hiloint2double(__float_as_int(q.y), __float_as_int(q.x)); }
@@ -717,7 +624,6 @@ __device__ bool boundary_t(const SceneView& S, uint32_t root, const Ray& r0, dou
     Closest cl;
     cl.set(tmax);
     bool found = false;
-    auto on_hit = [&](uint32_t, double) { found = true; };
     for (;;) {
         if (cur == REF_NONE) {
             cur = pop(stk, sp, sp0, cl.c_f);
@@ -745,12 +651,7 @@ __device__ bool boundary_t(const SceneView& S, uint32_t root, const Ray& r0, dou
         double t;
         switch (kind) {
             case K_BVH:
-                if constexpr (!BVH)
-                    break;
-                else if constexpr (RT_FULL_BVH4)
-                    cur = visit4_boxes(S, idx, rf, tmin_f, cl.c_f, stk, sp);
-                else
-                    cur = visit_node(S, idx, r, rf, a, inva, tmin, tmin_f, cl, stk, sp, on_hit);
+                if constexpr (BVH) cur = visit4_boxes(S, idx, rf, tmin_f, cl.c_f, stk, sp);
                 break;
             case K_SPHERE: {
                 const double4 s = S.spheres[idx];
@@ -771,7 +672,7 @@ __device__ bool boundary_t(const SceneView& S, uint32_t root, const Ray& r0, dou
             }
             case K_QUAD:
             case K_TRI:
-                if (planar_t_filtered(S, idx, kind == K_TRI, r, tmin, cl.c, cl.c_f, t)) {
+                if (planar_t(S.planars[idx], kind == K_TRI, r, tmin, cl.c, t)) {
                     cl.set(t);
                     found = true;
                 }
@@ -937,7 +838,7 @@ __device__ __forceinline__ void trace_begin(const SceneView& S, const Ray& wr, T
     T.found = false;
     T.hit.nxf = 0;
     T.nmed = 0;
-    if constexpr (TIER == TIER_BASIC && RT_BVH4) {
+    if constexpr (TIER == TIER_BASIC) {
         T.pn = 0;
         T.cur = bword(S, S.world_root);  // the 4-wide walk's cur is a walk word
     }
@@ -1045,6 +946,7 @@ struct MedQ {
 template <int TIER, class WR>
 __device__ __forceinline__ bool trace_step(const SceneView& S, const WR& wrr, Trav<TIER>& T, StackFor<TIER>& stk,
                                            const Rng& rng, MedQ med, Diag& dg) {
+    static_assert(TIER != TIER_BASIC, "the basic tier walks with trace4_step");
     const auto wq = world_ray(wrr);
     constexpr bool FULL = tier_full(TIER);
     constexpr double tmin = 1e-8;
@@ -1086,7 +988,7 @@ __device__ __forceinline__ bool trace_step(const SceneView& S, const WR& wrr, Tr
                 for (uint32_t k = 0; k < n; ++k) {
                     const bool tri = (run >> (8u + k)) & 1u;
                     double tt;
-                    if (planar_t_filtered(S, first + k, tri, r, tmin, T.cl.c, T.cl.c_f, tt)) {
+                    if (planar_t(S.planars[first + k], tri, r, tmin, T.cl.c, tt)) {
                         T.cl.set(tt);
                         record(make_ref(tri ? K_TRI : K_QUAD, first + k), tt);
                     }
@@ -1193,16 +1095,12 @@ __device__ __forceinline__ bool trace_step(const SceneView& S, const WR& wrr, Tr
         if (after != REF_NONE) T.cur = after;
         return true;
     }
-    if (TIER != TIER_FULL_FLAT && kind == K_BVH) {
-        if constexpr ((TIER == TIER_MESH && RT_MESH_BVH4) || (tier_full_bvh(TIER) && RT_FULL_BVH4))
-            T.cur = visit4_boxes(S, idx, T.rf, tmin_f, T.cl.c_f, stk, T.sp);
-        else
-            T.cur = visit_node(S, idx, r, T.rf, T.a, T.inva, tmin, tmin_f, T.cl, stk, T.sp, record);
-    } else if (kind == K_SPHERE) {
+    // (the flat tier's primitives -- it holds no BVH node -- and the full
+    // tiers' other kinds: nodes, spheres and planars of the BVH tiers took the
+    // unified load above)
+    if (kind == K_SPHERE) {
         const double4 sp4 = S.spheres[idx];
         got = sphere_t_inv(d3(sp4.x, sp4.y, sp4.z), sp4.w, r, T.a, T.inva, tmin, T.cl.c, t);
-    } else if constexpr (TIER == TIER_MESH) {
-        if (kind == K_TRI || kind == K_QUAD) got = planar_t_filtered(S, idx, kind == K_TRI, r, tmin, T.cl.c, T.cl.c_f, t);
     } else if constexpr (FULL) {
         switch (kind) {
             case K_MSPHERE: {
@@ -1212,7 +1110,7 @@ __device__ __forceinline__ bool trace_step(const SceneView& S, const WR& wrr, Tr
                 break;
             }
             case K_QUAD:
-            case K_TRI: got = planar_t_filtered(S, idx, kind == K_TRI, r, tmin, T.cl.c, T.cl.c_f, t); break;
+            case K_TRI: got = planar_t(S.planars[idx], kind == K_TRI, r, tmin, T.cl.c, t); break;
             case K_XFORM: {
                 const DXform& X = S.xforms[idx];
                 stk.push(T.sp++, make_ref(K_POPXF, 0), NO_CULL);
@@ -1326,9 +1224,6 @@ __device__ __forceinline__ Node4Rows load_node4(const RT_LDS float4* nl, uint32_
     const RT_LDS float4* np = nl + idx * 7u;
     return Node4Rows{np[0], np[1], np[2], np[3], np[4], np[5], np[6]};
 }
-#ifndef RT_SPHERE_RINV
-#define RT_SPHERE_RINV 1  // basic / mesh tiers: a static sphere's 1.0 / r from the flatten, not divided per hit
-#endif
 // visit4 on node rows already loaded; the ref row holds walk words (bword)
 template <class Stack>
 __device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4Rows& nr, const RayF& rf, float tmin_f,
@@ -1584,7 +1479,7 @@ __device__ Rec make_record(const SceneView& S, const Ray& wr, const HitInfo& h, 
             c = d3(s.x, s.y, s.z);
             // basic / mesh tiers: the host's 1.0 / r, the same double (C2 -0.5 %);
             // the full tiers divide (C5 +1.0 % with the load: A/B, RMSE 0)
-            rinv = (RT_SPHERE_RINV && !FULL) ? S.sphere_rinv[idx] : 1.0 / s.w;
+            rinv = !FULL ? S.sphere_rinv[idx] : 1.0 / s.w;
             rec.mat = S.sphere_mat[idx];
         } else {
             const double4 s = S.msph_center[idx], m = S.msph_dir[idx];
@@ -1883,7 +1778,7 @@ template <int D>
 __device__ D3 emitted_tree(const SceneView& S, int mid, double u, double v, D3 p) {
     const DMaterial& M = S.materials[mid];
     if (M.type == M_DIFFUSE_LIGHT) {
-        const D3 self = mat_tex<true, RT_PERLIN_LDS>(S, M, u, v, p);
+        const D3 self = mat_tex<true, true>(S, M, u, v, p);
         D3 inner = d3(0.0, 0.0, 0.0);
         if constexpr (D > 0)
             if (M.inner >= 0) inner = emitted_tree<D - 1>(S, M.inner, u, v, p);
@@ -1901,46 +1796,11 @@ __device__ D3 emitted_tree(const SceneView& S, int mid, double u, double v, D3 p
 // ------------------------------------------------------------------ one ray_color level
 // camera.rs:275-325 at path vertex `vertex`; updates (ray, beta, L).  Returns
 // true when the path ends here (miss, no scatter, panic).
-// Deferred shading classes (full BVH tier, A/B lever): a lane whose hit is
-// a plain Lambertian with a texture kind in RT_SHADE_DEFER_TEX_MASK (a bit per
-// T_*) skips a shading round while fewer than RT_SHADE_DEFER_K such lanes are
-// ready, other lanes still walk, and the wave has deferred fewer than
-// RT_SHADE_DEFER_WAIT rounds in a row.  It keeps its hit, its RNG state and its
-// path and is shaded in a later round, with the same doubles (nothing it
-// computes depends on when).  0: off -- measured on C5 (64 spp, 4 reps, the
-// tier's product flags, RMSE 0): +0.5 % to +1.6 % kernel time, the noise
-// class's share of rounds 38 % -> 22 % but VALU exec density unchanged
-// (0.3383) and walk lane efficiency 0.628 -> 0.611
-// (profiles/r06/ab_shade_defer_t2flags_c5_64spp.json, density_c5_t2*.json).
-#ifndef RT_SHADE_DEFER
-#define RT_SHADE_DEFER 0
-#endif
-#ifndef RT_SHADE_DEFER_TEX_MASK
-#define RT_SHADE_DEFER_TEX_MASK (1u << T_NOISE)
-#endif
-#ifndef RT_SHADE_DEFER_K
-#define RT_SHADE_DEFER_K 12
-#endif
-#ifndef RT_SHADE_DEFER_WAIT
-#define RT_SHADE_DEFER_WAIT 3
-#endif
-// RT_SHADE_DEFER: the hit's material is a plain (non-emissive) Lambertian whose
-// texture kind is in RT_SHADE_DEFER_TEX_MASK
-__device__ __forceinline__ bool shade_deferrable(const SceneView& S, uint32_t ref) {
-    const uint32_t k = ref_kind(ref), i = ref_index(ref);
-    const int32_t m = k == K_SPHERE ? S.sphere_mat[i] : k == K_MSPHERE ? S.msph_mat[i]
-                    : (k == K_QUAD || k == K_TRI) ? S.planar_mat[i] : -1;
-    if (m < 0) return false;
-    const DMaterial& M = S.materials[m];
-    if (M.type != M_LAMBERTIAN || (M.flags & (MF_SOLID | MF_EMISSIVE))) return false;
-    return ((RT_SHADE_DEFER_TEX_MASK >> S.textures[M.tex].type) & 1u) != 0u;
-}
-
 template <int TIER>
 __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3& L, Rng& rng, bool hit_any,
                                       const HitInfo& h, bool& panic, const Draws& Dr = Draws{}) {
     constexpr bool FULL = tier_full(TIER);
-    constexpr bool PL = tier_full_bvh(TIER) && RT_PERLIN_LDS;  // the block holds the LDS copy of the first Perlin table (the flat tier's LDS is full)
+    constexpr bool PL = tier_full_bvh(TIER);  // the block holds the LDS copy of the first Perlin table (the flat tier's LDS is full)
     uint32_t ovf = 0;
     if (!hit_any) {
         // miss: Environment::value (environment.rs:14-24)
@@ -1959,16 +1819,14 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
             // (0 * inf), gives a NaN (tests/test_miss_unit_cpu.py)
             // The gradient's colours come with the launch parameters
             // (SceneView::bg_c0 / bg_c1), not from the texture table.
-            if (RT_BG_PARAMS ? S.bg_kind == BG_SKY
-                             : (S.background_tex >= 0 && S.textures[S.background_tex].type == T_SKY)) {
+            if (S.bg_kind == BG_SKY) {
                 const double l = len(ray.d);
                 if (isnan(l) || l == 0.0 || !finite3(ray.d)) panic = true;
-                L = L + beta * (RT_BG_PARAMS ? sky_value(S.bg_c0, S.bg_c1, (1.0 / l) * ray.d.y)
-                                             : sky_value(S.textures[S.background_tex], (1.0 / l) * ray.d.y));
+                L = L + beta * sky_value(S.bg_c0, S.bg_c1, (1.0 / l) * ray.d.y);
                 return true;
             }
         }
-        if (RT_BG_PARAMS && !FULL && S.bg_kind == BG_SKY) {  // the mesh tier: unit(), the gradient from the launch parameters
+        if (!FULL && S.bg_kind == BG_SKY) {  // the mesh tier: unit(), the gradient from the launch parameters
             bool ok;
             const D3 p = unit(ray.d, ok);
             if (!ok) panic = true;
@@ -2167,11 +2025,6 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
 }
 
 // ------------------------------------------------------------------ basic tier: one hit, merged
-#ifndef RT_SHADE_MERGED
-// 1: the basic tier shades a hit with shade_hit_basic (below), 0: with shade
-// (A/B only)
-#define RT_SHADE_MERGED 1
-#endif
 // shade() for a hit in the basic tier (camera.rs:286-316; Lambertian /
 // EmptyMaterial, Metal, Dielectric: material.rs:41-143, onb.rs:8-38,
 // pdf.rs:50-63), with the three scatter codes' square roots and divisions
@@ -2427,7 +2280,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     __shared__ uint32_t stack4_lds[B4 ? STACK * BLK : 1];
     RT_LDS uint2* const lrow = (RT_LDS uint2*)(lane_lds + threadIdx.x);
     const MedQ med{lrow + R_MED * BLK};
-    __shared__ uint16_t pend_lds[TIER == TIER_BASIC && RT_BVH4 ? RT_PEND_CAP * BLK : 1];
+    __shared__ uint16_t pend_lds[B4 ? RT_PEND_CAP * BLK : 1];
     RT_LDS uint16_t* pq = (RT_LDS uint16_t*)(pend_lds + threadIdx.x);
     StackFor<TIER> stk = make_stack<TIER>(lrow, (RT_LDS uint32_t*)(stack4_lds + threadIdx.x),
                                           P->stack_ovf + (uint64_t)blockIdx.x * BLK + threadIdx.x, gridDim.x * BLK);
@@ -2442,8 +2295,8 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     RT_LDS uint2* pk2 = (RT_LDS uint2*)park_lds + threadIdx.x;  // basic tier: 8-byte rows (trace_park2)
     // Basic tier: the block's copy of the world's 4-wide nodes (the whole tree:
     // 241 nodes for C1/C2), read by every node visit instead of global memory.
-    __shared__ float4 node_lds[TIER == TIER_BASIC && RT_BVH4 ? NODE_CAP * 7 : 1];
-    if constexpr (TIER == TIER_BASIC && RT_BVH4) {
+    __shared__ float4 node_lds[B4 ? NODE_CAP * 7 : 1];
+    if constexpr (B4) {
         const uint32_t n_lds = min(S.n_nodes4, NODE_CAP);  // == n_nodes4 (launcher: rtk_launch_frame)
         const RT_GLOBAL float4* src = reinterpret_cast<const RT_GLOBAL float4*>(S.nodes4);
         for (uint32_t k = threadIdx.x; k < n_lds * 7u; k += BLK) {
@@ -2458,7 +2311,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         }
         __syncthreads();
     }
-    if constexpr (tier_full_bvh(TIER) && RT_PERLIN_LDS) {
+    if constexpr (tier_full_bvh(TIER)) {
         if (S.n_perlin > 0) {
             const RT_GLOBAL float4* src = reinterpret_cast<const RT_GLOBAL float4*>(S.perlin);
             RT_LDS float4* dst = (RT_LDS float4*)&g_perlin_lds;
@@ -2505,11 +2358,6 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     Diag dg;
     Trav<TIER> T;
     bool walking = false;
-    // RT_SHADE_DEFER (full BVH tier): this lane's finished walk waits for a later
-    // shading round; the wave's count of rounds deferred in a row
-    constexpr bool DEFER = RT_SHADE_DEFER && TIER == TIER_FULL;
-    bool deferred = false;
-    uint32_t defer_rounds = 0;
 #ifdef RT_WAVE_TRACE
     const uint32_t trace_lane = blockIdx.x * BLK + threadIdx.x;
     const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
@@ -2610,12 +2458,10 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         acc = acc + L;
         ++s_j;
         if (s_j == (sie >> 16)) {
-#ifndef RT_MEASURE_NOSTORE
             double* dst = P->partial + (uint64_t)slot * 3;
             dst[0] = acc.x;
             dst[1] = acc.y;
             dst[2] = acc.z;
-#endif
             need = true;
         }
     };
@@ -2626,16 +2472,14 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         // both (struct Draws).  A lane whose path ends in shading (depth,
         // panic, no scatter) starts its next sample one iteration later.
         bool no_path = true;  // the lane starts a sample at its next post-walk stage
-        constexpr int BATCH = TIER == TIER_BASIC ? BASIC_BATCH : RT_SHADE_BATCH_MESH;
+        constexpr int BATCH = BASIC_BATCH;
         // ---- Camera::get_ray (camera.rs:247-273), vertex 0, from the iteration's draws
         auto camera_ray = [&](const Draws& Dr) {
             const uint32_t s_i = sie & 0xFFFFu, py = udiv_inv(rng.pixel, F.inv_W), px = rng.pixel - py * F.W;
             double xi0 = Dr.xi0, xi1 = Dr.xi1;
             D3 origin = F.center;
             if (F.defocus) {  // vec3.rs:63-69: theta = 2 pi Dr.xi0, r = sqrt(Dr.xi1)
-#ifndef RT_MEASURE_NOCAMPAIR
                 rng.pair(0u, 0u, xi0, xi1);
-#endif
                 const double rr = k_sqrt(Dr.xi1);
                 origin = (F.center + ((rr * Dr.cs) * F.disk_u)) + ((rr * Dr.sn) * F.disk_v);
             }
@@ -2695,12 +2539,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
             RT_DIAG_ONLY(const unsigned long long t_b0 = __builtin_amdgcn_s_memtime(); dg.cyc_refill += t_b0 - t_loop0;)
             RT_ISA_MARK("walk");
             auto step = [&]() -> bool {
-                if constexpr (TIER == TIER_BASIC && RT_BVH4) {
-                    return trace4_step(S, ray, T, stk, pq, (const RT_LDS float4*)node_lds, dg);
-                } else {
-                    RT_DIAG_ONLY(if (__lane_id() == (uint32_t)(__ffsll((long long)__ballot(true)) - 1)) ++dg.wave_trace_iters; ++dg.lane_trace_iters;)
-                    return trace_step<TIER>(S, ray, T, stk, rng, med, dg);
-                }
+                return trace4_step(S, ray, T, stk, pq, (const RT_LDS float4*)node_lds, dg);
             };
             if constexpr (BATCH >= 64) {
 #ifdef RT_WAVE_TRACE
@@ -2731,11 +2570,9 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
             bool cam = no_path;
             if (!carry && !no_path && !T.found) {  // a miss: Environment::value, and the sample ends
                 RT_ISA_MARK("miss");
-#ifndef RT_MEASURE_NOSKY
                 bool panic = false;
                 shade<TIER>(S, ray, beta, L, rng, false, T.hit, panic);
                 if (panic) ++n_panics;
-#endif
                 finish_sample();
                 cam = true;
             }
@@ -2761,7 +2598,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                 rng.slot = 2;  // slots 0 and 1 are Dr
                 bool panic = false;
                 bool end_path;
-                if constexpr (TIER == TIER_BASIC && RT_SHADE_MERGED && !WIDE)  // (the wide variant spills 76 B/lane with it)
+                if constexpr (!WIDE)  // (the wide variant spills 76 B/lane with the merged stages)
                     end_path = shade_hit_basic(S, ray, beta, T.hit, panic, Dr);
                 else
                     end_path = shade<TIER>(S, ray, beta, L, rng, true, T.hit, panic, Dr);
@@ -2903,7 +2740,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
 #ifdef RT_WAVE_TRACE
         hist.add(__ballot(!walking));
 #endif
-        if (!walking && !(DEFER && deferred)) {
+        if (!walking) {
             rng.begin(vertex);
             ++n_rays;
             trace_begin<TIER>(S, ray, T);
@@ -2912,20 +2749,15 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
             trace_unpark(ray, T, pk);  // a walk carried over the last shading round
         }
         RT_DIAG_ONLY(const unsigned long long t_b0 = __builtin_amdgcn_s_memtime(); dg.cyc_refill += t_b0 - t_loop0;)
-        constexpr int BATCH = TIER == TIER_BASIC ? BASIC_BATCH
-                            : TIER == TIER_MESH ? RT_SHADE_BATCH_MESH
+        constexpr int BATCH = TIER == TIER_MESH ? RT_SHADE_BATCH_MESH
                             : TIER == TIER_FULL ? RT_SHADE_BATCH_FULL : RT_SHADE_BATCH_FLAT;
         auto step = [&]() -> bool {
-            if constexpr (TIER == TIER_BASIC && RT_BVH4) {
-                return trace4_step(S, ray, T, stk, pq, (const RT_LDS float4*)node_lds, dg);
-            } else {
-                // every step call of the lane (the basic tier counts its own)
-                RT_DIAG_ONLY(if (__lane_id() == (uint32_t)(__ffsll((long long)__ballot(true)) - 1)) ++dg.wave_trace_iters; ++dg.lane_trace_iters;)
-                if constexpr (PARK_RAY)
-                    return trace_step<TIER>(S, RayLds{pst + 9 * RT_BLOCK}, T, stk, rng, med, dg);
-                else
-                    return trace_step<TIER>(S, ray, T, stk, rng, med, dg);
-            }
+            // every step call of the lane (the basic tier counts its own)
+            RT_DIAG_ONLY(if (__lane_id() == (uint32_t)(__ffsll((long long)__ballot(true)) - 1)) ++dg.wave_trace_iters; ++dg.lane_trace_iters;)
+            if constexpr (PARK_RAY)
+                return trace_step<TIER>(S, RayLds{pst + 9 * RT_BLOCK}, T, stk, rng, med, dg);
+            else
+                return trace_step<TIER>(S, ray, T, stk, rng, med, dg);
         };
         if constexpr (BATCH >= 64) {  // the whole wave finishes its walks, then shades
             if constexpr (LDS_STATE) {
@@ -2967,23 +2799,10 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         RT_DIAG_ONLY(const unsigned long long t_b1 = __builtin_amdgcn_s_memtime(); dg.cyc_trace += t_b1 - t_b0;)
         if constexpr (BATCH < 64 && tier_full(TIER)) {
             RT_DIAG_ONLY(const unsigned long long t_mb = __builtin_amdgcn_s_memtime();)
-            if (!walking && !(DEFER && deferred)) media_phase<TIER>(S, ray, T, stk, rng, med);
+            if (!walking) media_phase<TIER>(S, ray, T, stk, rng, med);
             RT_DIAG_ONLY(dg.cyc_media += __builtin_amdgcn_s_memtime() - t_mb;)
         }
-        if constexpr (DEFER) {
-            // wave-uniform: defer this round's candidates while few are ready,
-            // other lanes still walk, and the wave has not waited too long
-            const bool others = __ballot(walking) != 0ull;
-            const unsigned long long cm = __ballot(!walking && T.found && shade_deferrable(S, T.hit.ref));
-            if (cm != 0ull && others && __popcll(cm) < RT_SHADE_DEFER_K && defer_rounds < RT_SHADE_DEFER_WAIT) {
-                ++defer_rounds;
-                if ((cm >> __lane_id()) & 1ull) deferred = true;
-            } else {
-                defer_rounds = 0;
-                deferred = false;
-            }
-        }
-        if (BATCH < 64 && (walking || (DEFER && deferred))) {
+        if (BATCH < 64 && walking) {
             if constexpr (PARK) trace_park(T, pk);
             continue;
         }
@@ -3476,15 +3295,9 @@ __global__ void __launch_bounds__(256) rt_deinterleave_u8_kernel(const uint8_t* 
 }
 }  // namespace rtk
 
-extern "C" int rtk_tier_for(uint32_t features, uint32_t stack_need) {
-    return rtk::plan::tier_for(features, stack_need, RT_BVH4 != 0, RT_STACK_BASIC);
-}
+extern "C" int rtk_tier_for(uint32_t features) { return rtk::plan::tier_for(features); }
 
-extern "C" int rtk_basic_bvh4(void) { return RT_BVH4; }
-extern "C" int rtk_planar_filter(void) { return RT_PLANAR_FILTER; }
 extern "C" int rtk_block_threads(int tier) { return tier == rtk::TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK; }
-extern "C" int rtk_mesh_bvh4(void) { return RT_MESH_BVH4; }
-extern "C" int rtk_full_bvh4(void) { return RT_FULL_BVH4; }
 
 extern "C" uint32_t rtk_stack_entries(int tier) {
     return tier == rtk::TIER_BASIC ? RT_STACK_BASIC : RT_STACK_MAX;

@@ -53,13 +53,12 @@ __host__ __device__ inline uint32_t ref_kind(uint32_t r) { return r >> 28; }
 __host__ __device__ inline uint32_t ref_index(uint32_t r) { return r & 0x0FFFFFFFu; }
 constexpr uint32_t REF_NONE = 0u;
 
-// BVH node (bvh.rs:5-9 re-laid out): the parent carries what is needed to
-// test each child, so one node visit is one 80-B record:
-//  - a child that is a sphere stores the sphere itself (f64 center, radius:
-//    the exact data Sphere::hit reads, sphere.rs:77-108), tested directly --
-//    no box test, no dependent load;
+// Two-box BVH node (bvh.rs:5-9 re-laid out), host side only: what the BVH
+// builders make and rth::bvh4_convert collapses into DNode4; no kernel walks
+// it.  The parent carries what is needed to test each child:
+//  - a child that is a sphere stores the sphere itself (f64 center, radius);
 //  - any other child stores its AABB as f32 rounded outward (lo down, hi up);
-//    the slab test is made conservative (rt_kernel.hip slab_f), so every hit
+//    the slab test is made conservative (rt_slab.h slab_f), so every hit
 //    the reference's exact-box f64 test admits is admitted.
 // c1 may be REF_NONE (a BVH over one object, bvh.rs:25).
 struct alignas(16) DNodeSlot {
@@ -78,9 +77,9 @@ struct alignas(16) DNode {
 };
 static_assert(sizeof(DNode) == 80, "DNode must be 80 B (5 dwordx4)");
 
-// Basic-tier 4-wide BVH node (rth::bvh4_basic): up to four children, their
-// f32 boxes (rounded outward) stored component-major so one dwordx4 holds one
-// bound of all four.  A sphere child's box is its own, c -+ r widened by a hair
+// 4-wide BVH node (rth::bvh4_convert): up to four children, their f32 boxes
+// (rounded outward) stored component-major so one dwordx4 holds one bound of
+// all four.  Basic tier: a sphere child's box is its own, c -+ r widened by a hair
 // and rounded outward (rt_slab.h sphere_box_f): the walk slab-tests it like any
 // other child's and queues the sphere for the exact f64 test on a hit.
 struct alignas(16) DNode4 {
@@ -209,7 +208,7 @@ struct alignas(16) DPerlin {
 
 // Everything the kernel reads about the world, as device pointers.
 struct SceneView {
-    const RT_GLOBAL DNode* nodes;
+    const RT_GLOBAL DNode* nodes;            // unused (no kernel walks the two-box nodes): always empty
     const RT_GLOBAL DNode4* nodes4;          // 4-wide nodes: K_BVH refs index these
     const RT_GLOBAL double4* spheres;        // {cx, cy, cz, r}
     const RT_GLOBAL int32_t* sphere_mat;
@@ -218,7 +217,7 @@ struct SceneView {
     const RT_GLOBAL double4* msph_dir;       // {c2-c1, 0}
     const RT_GLOBAL int32_t* msph_mat;
     const RT_GLOBAL DPlanar* planars;        // quads then triangles share the record
-    const RT_GLOBAL PlanarF* planars_f;      // their f32 pre-test records (rt_planar_filter.h)
+    const RT_GLOBAL PlanarF* planars_f;      // unused (rt_planar_filter.h: no kernel runs the pre-test): null
     const RT_GLOBAL double* planar_area;
     const RT_GLOBAL int32_t* planar_mat;
     const RT_GLOBAL int32_t* planar_remap;   // index into remaps, -1 = plain Triangle/Quad
@@ -245,7 +244,7 @@ struct SceneView {
     uint32_t features;       // F_* of everything reachable from world/lights
     uint32_t n_nodes4;       // entries of nodes4
     uint32_t n_perlin;       // entries of perlin (the full tiers copy the first into LDS)
-    // records each ref kind indexes (K_BVH: nodes4 or the two-box nodes,
+    // records each ref kind indexes (K_BVH: nodes4,
     // K_LIST: list_children, K_QUAD / K_TRI: planars, ...): the check build
     // (make check, -DRT_CHECK) verifies every decoded ref against it
     uint32_t n_ref[16];

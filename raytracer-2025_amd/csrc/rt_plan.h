@@ -16,17 +16,13 @@ namespace rtk {
 namespace plan {
 
 // The smallest kernel tier covering a flattened world's features (rt_kernel.h
-// Tier).  bvh4: the basic tier walks 4-wide nodes, whose stack need the
-// launcher checks itself (rt_render.cpp prepare_tier).
-inline int tier_for(uint32_t features, uint32_t stack_need, bool bvh4, uint32_t stack_basic) {
+// Tier).  Whether a basic-tier world's 4-wide tree fits the basic kernel's
+// stack and node copy the launcher checks itself (rt_render.cpp prepare_tier).
+inline int tier_for(uint32_t features) {
     const uint32_t full = F_XFORM | F_MEDIUM | F_MSPHERE | F_LIGHTS | F_TEXFULL | F_MATFULL | F_NORMALMAP;
     if (features & F_GENERAL) return 4;          // TIER_FULL_GL
     if (features & full) return 2;               // TIER_FULL
     if (features & (F_PLANAR | F_REMAP)) return 1;  // TIER_MESH
-    // the two-box tree's stack need; with 4-wide nodes the launcher decides on
-    // the 4-wide tree's (shallower: a 1 500-sphere world needs 22 entries as
-    // two-box nodes and fits the basic tier's 14 as 4-wide ones)
-    if (!bvh4 && stack_need > stack_basic) return 1;
     return 0;  // TIER_BASIC
 }
 

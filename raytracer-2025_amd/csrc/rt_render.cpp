@@ -277,24 +277,23 @@ void destroy_render_state(RenderState* r) {
 }
 
 // The kernel tier for a flattened world, with the tier's node format applied:
-// the basic and mesh tiers walk 4-wide BVH nodes; a world whose 4-wide nodes
-// would need more stack than the tier holds moves up a tier (the basic tier's
-// LDS stack -> the mesh tier -> the full tier, whose walk has no fallback:
-// -1 with RT_ESTACK set).
+// every BVH tier walks 4-wide nodes (bvh4_convert, which leaves hw as it was
+// when it fails); a world whose 4-wide nodes would need more stack than the
+// tier holds moves up a tier (the basic tier's LDS stack -> the mesh tier ->
+// the full tier, whose walk has no fallback: -1 with RT_ESTACK set).
 static int prepare_tier(HostWorld& hw) {
-    int tier = rtk_tier_for(hw.features, hw.stack_need);
+    int tier = rtk_tier_for(hw.features);
     // the basic tier's walk words hold 15-bit sphere indices (rt_kernel.hip bword)
     if (tier == rtk::TIER_BASIC && hw.spheres.size() > 32768) tier = rtk::TIER_MESH;
     // and its 4-B stack entries hold 15-bit node / list indices
     if (tier == rtk::TIER_BASIC && hw.list_children.size() >= 32768) tier = rtk::TIER_MESH;
     // the basic tier's kernel reads every 4-wide node from its LDS copy
-    if (tier == rtk::TIER_BASIC && rtk_basic_bvh4() &&
+    if (tier == rtk::TIER_BASIC &&
         bvh4_convert(hw, RT_STACK_BASIC, true, RT_NODE_LDS_BYTES / sizeof(rtk::DNode4)) > RT_STACK_BASIC)
         tier = rtk::TIER_MESH;
-    if (tier == rtk::TIER_MESH && rtk_mesh_bvh4() && bvh4_convert(hw, RT_STACK_MAX, false) > RT_STACK_MAX)
-        tier = rtk::TIER_FULL;
+    if (tier == rtk::TIER_MESH && bvh4_convert(hw, RT_STACK_MAX, false) > RT_STACK_MAX) tier = rtk::TIER_FULL;
     if (tier == rtk::TIER_FULL && hw.nodes.empty()) return rtk::TIER_FULL_FLAT;
-    if (rtk::tier_full_bvh(tier) && rtk_full_bvh4()) {
+    if (rtk::tier_full_bvh(tier)) {
         const uint32_t need = bvh4_convert(hw, RT_STACK_MAX, false);
         if (need > RT_STACK_MAX) {
             set_error(RT_ESTACK, "world needs " + std::to_string(need) + " traversal-stack entries, kernel has " +
@@ -315,6 +314,40 @@ static size_t put(std::vector<char>& blob, const std::vector<T>& v) {
     blob.resize(off + v.size() * sizeof(T));
     if (!v.empty()) std::memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
     return off;
+}
+
+// The world blob a render uploads: every array of a flattened world (after
+// prepare_tier) at a 256-B boundary, and v's array pointers as byte offsets
+// into it.
+static void pack_world(const HostWorld& hw, std::vector<char>& blob, rtk::SceneView& v) {
+    auto off = [](size_t o) { return (uintptr_t)o; };
+    v.nodes = (const rtk::DNode*)off(put(blob, hw.nodes));
+    v.nodes4 = (const rtk::DNode4*)off(put(blob, hw.nodes4));
+    v.spheres = (const double4*)off(put(blob, hw.spheres));
+    v.sphere_mat = (const int32_t*)off(put(blob, hw.sphere_mat));
+    v.sphere_rinv = (const double*)off(put(blob, hw.sphere_rinv));
+    v.msph_center = (const double4*)off(put(blob, hw.msph_center));
+    v.msph_dir = (const double4*)off(put(blob, hw.msph_dir));
+    v.msph_mat = (const int32_t*)off(put(blob, hw.msph_mat));
+    v.planars = (const rtk::DPlanar*)off(put(blob, hw.planars));
+    v.planars_f = nullptr;  // (no kernel reads it)
+    v.planar_area = (const double*)off(put(blob, hw.planar_area));
+    v.planar_mat = (const int32_t*)off(put(blob, hw.planar_mat));
+    v.planar_remap = (const int32_t*)off(put(blob, hw.planar_remap));
+    v.remaps = (const rtk::DRemap*)off(put(blob, hw.remaps));
+    v.remap_nm = (const rtk::DRemapNM*)off(
+        put(blob, (hw.features & rtk::F_NORMALMAP) ? hw.remap_nm : std::vector<rtk::DRemapNM>()));
+    v.list_children = (const uint32_t*)off(put(blob, hw.list_children));
+    v.list_boxes = (const rtk::DBoxF*)off(put(blob, hw.list_boxes));
+    v.xforms = (const rtk::DXform*)off(put(blob, hw.xforms));
+    v.media = (const rtk::DMedium*)off(put(blob, hw.media));
+    v.materials = (const rtk::DMaterial*)off(put(blob, hw.materials));
+    v.textures = (const rtk::DTexture*)off(put(blob, hw.textures));
+    v.texels = (const float*)off(put(blob, hw.texels));
+    v.perlin = (const rtk::DPerlin*)off(put(blob, hw.perlin));
+    // the mesh tier reads 128 B from any record's address (rt_kernel.hip
+    // unified_load): slack past the last array
+    blob.resize(((blob.size() + 255) & ~(size_t)255) + 256, 0);
 }
 
 // The world of one render flattened once on the host and shared by every
@@ -370,36 +403,8 @@ static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg
         fw.err = rt_last_error();
         return rc;
     }
-    std::vector<char>& blob = fw.blob;
-    auto off = [](size_t o) { return (uintptr_t)o; };
     rtk::SceneView& v = fw.rel;
-    v.nodes = (const rtk::DNode*)off(put(blob, hw.nodes));
-    v.nodes4 = (const rtk::DNode4*)off(put(blob, hw.nodes4));
-    v.spheres = (const double4*)off(put(blob, hw.spheres));
-    v.sphere_mat = (const int32_t*)off(put(blob, hw.sphere_mat));
-    v.sphere_rinv = (const double*)off(put(blob, hw.sphere_rinv));
-    v.msph_center = (const double4*)off(put(blob, hw.msph_center));
-    v.msph_dir = (const double4*)off(put(blob, hw.msph_dir));
-    v.msph_mat = (const int32_t*)off(put(blob, hw.msph_mat));
-    v.planars = (const rtk::DPlanar*)off(put(blob, hw.planars));
-    v.planars_f = (const rtk::PlanarF*)off(put(blob, hw.planars_f));
-    v.planar_area = (const double*)off(put(blob, hw.planar_area));
-    v.planar_mat = (const int32_t*)off(put(blob, hw.planar_mat));
-    v.planar_remap = (const int32_t*)off(put(blob, hw.planar_remap));
-    v.remaps = (const rtk::DRemap*)off(put(blob, hw.remaps));
-    v.remap_nm = (const rtk::DRemapNM*)off(
-        put(blob, (hw.features & rtk::F_NORMALMAP) ? hw.remap_nm : std::vector<rtk::DRemapNM>()));
-    v.list_children = (const uint32_t*)off(put(blob, hw.list_children));
-    v.list_boxes = (const rtk::DBoxF*)off(put(blob, hw.list_boxes));
-    v.xforms = (const rtk::DXform*)off(put(blob, hw.xforms));
-    v.media = (const rtk::DMedium*)off(put(blob, hw.media));
-    v.materials = (const rtk::DMaterial*)off(put(blob, hw.materials));
-    v.textures = (const rtk::DTexture*)off(put(blob, hw.textures));
-    v.texels = (const float*)off(put(blob, hw.texels));
-    v.perlin = (const rtk::DPerlin*)off(put(blob, hw.perlin));
-    // the mesh tier reads 128 B from any record's address (rt_kernel.hip
-    // unified_load): slack past the last array
-    blob.resize(((blob.size() + 255) & ~(size_t)255) + 256, 0);
+    pack_world(hw, fw.blob, v);
     v.world_root = hw.world_root;
     v.lights_root = hw.lights_root;
     v.background_tex = bg;
@@ -417,7 +422,7 @@ static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg
     v.n_nodes4 = (uint32_t)hw.nodes4.size();
     v.n_perlin = (uint32_t)hw.perlin.size();
     std::memset(v.n_ref, 0, sizeof v.n_ref);
-    v.n_ref[rtk::K_BVH] = (uint32_t)std::max(hw.nodes4.size(), hw.nodes.size());
+    v.n_ref[rtk::K_BVH] = (uint32_t)hw.nodes4.size();
     v.n_ref[rtk::K_LIST] = (uint32_t)hw.list_children.size();
     v.n_ref[rtk::K_SPHERE] = (uint32_t)hw.spheres.size();
     v.n_ref[rtk::K_MSPHERE] = (uint32_t)hw.msph_center.size();
@@ -509,7 +514,7 @@ static int32_t upload_world(rt_scene* s, DeviceWorld* d, int32_t world, int32_t 
     rtk::SceneView v = fw.rel;
     auto fix = [b](auto& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + (uintptr_t)p); };
     fix(v.nodes), fix(v.nodes4), fix(v.spheres), fix(v.sphere_mat), fix(v.sphere_rinv), fix(v.msph_center), fix(v.msph_dir),
-        fix(v.msph_mat), fix(v.planars), fix(v.planars_f), fix(v.planar_area), fix(v.planar_mat), fix(v.planar_remap), fix(v.remaps),
+        fix(v.msph_mat), fix(v.planars), fix(v.planar_area), fix(v.planar_mat), fix(v.planar_remap), fix(v.remaps),
         fix(v.remap_nm), fix(v.list_children), fix(v.list_boxes), fix(v.xforms), fix(v.media), fix(v.materials), fix(v.textures),
         fix(v.texels), fix(v.perlin);
     d->view = v;
@@ -1068,19 +1073,15 @@ int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t bg
         HostWorld hw;
         int32_t rc = flatten(s, world, lights, bg, (flags & RT_FLAG_REFERENCE_BVH) != 0, hw);
         if (rc != RT_OK) return rc;
-        std::vector<char> blob;
-        put(blob, hw.nodes), put(blob, hw.spheres), put(blob, hw.sphere_mat), put(blob, hw.sphere_rinv),
-            put(blob, hw.msph_center),
-            put(blob, hw.msph_dir), put(blob, hw.msph_mat), put(blob, hw.planars), put(blob, hw.planar_area),
-            put(blob, hw.planar_mat), put(blob, hw.list_children), put(blob, hw.xforms), put(blob, hw.media),
-            put(blob, hw.materials), put(blob, hw.textures), put(blob, hw.texels), put(blob, hw.perlin);
-        out->device_bytes = blob.size();
-        out->bvh_nodes = (uint32_t)hw.nodes.size();
         out->primitives = (uint32_t)hw.n_prims;
         out->bvh_leaves = (uint32_t)hw.n_bvh_leaves;
         const int tier = prepare_tier(hw);
         if (tier < 0) return RT_ESTACK;
-        if (!hw.nodes4.empty()) out->bvh_nodes = (uint32_t)hw.nodes4.size();
+        std::vector<char> blob;  // what a render of this world uploads
+        rtk::SceneView view{};
+        pack_world(hw, blob, view);
+        out->device_bytes = blob.size();
+        out->bvh_nodes = (uint32_t)hw.nodes4.size();
         out->stack_need = hw.stack_need;
         out->kernel_tier = (uint32_t)tier;
         out->features = hw.features;

@@ -106,15 +106,14 @@ struct MatRec {
 
 // Flattened world on the host, ready to upload as one blob.
 struct HostWorld {
-    std::vector<rtk::DNode> nodes;
-    std::vector<rtk::DNode4> nodes4;  // basic tier (bvh4_basic); mesh / full tiers before bvh4_quantize
+    std::vector<rtk::DNode> nodes;    // the builder's two-box nodes: bvh4_convert's input, empty after it
+    std::vector<rtk::DNode4> nodes4;  // the 4-wide nodes the kernels walk (bvh4_convert)
     std::vector<double4> spheres;
     std::vector<int32_t> sphere_mat;
     std::vector<double> sphere_rinv;  // 1.0 / radius, the factor of sphere.rs:99's (p - c) / radius
     std::vector<double4> msph_center, msph_dir;
     std::vector<int32_t> msph_mat;
     std::vector<rtk::DPlanar> planars;
-    std::vector<rtk::PlanarF> planars_f;  // parallel to planars
     std::vector<double> planar_area;
     std::vector<int32_t> planar_mat;
     std::vector<int32_t> planar_remap;

@@ -292,14 +292,8 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
 }
 
 // ---------------------------------------------------------------- rt_kernel.h
-int rtk_tier_for(uint32_t features, uint32_t stack_need) {
-    return rtk::plan::tier_for(features, stack_need, true, RT_STACK_BASIC);
-}
+int rtk_tier_for(uint32_t features) { return rtk::plan::tier_for(features); }
 uint32_t rtk_stack_entries(int tier) { return tier == rtk::TIER_BASIC ? RT_STACK_BASIC : RT_STACK_MAX; }
-int rtk_basic_bvh4(void) { return 1; }
-int rtk_mesh_bvh4(void) { return 1; }
-int rtk_full_bvh4(void) { return 1; }
-int rtk_planar_filter(void) { return 0; }
 int rtk_block_threads(int tier) { return tier == rtk::TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK; }
 uint32_t rtk_row_parts(uint32_t S, uint32_t part_samples) { return rtk::plan::row_parts(S, part_samples); }
 uint32_t rtk_tail_rows(uint32_t W, uint32_t H, uint32_t S, uint32_t parts, uint64_t budget, uint32_t permille) {

@@ -55,7 +55,6 @@ namespace rth {
 struct RenderState;
 void destroy_render_state(RenderState*) {}
 }  // namespace rth
-extern "C" int rtk_planar_filter(void) { return 0; }  // the product's RT_PLANAR_FILTER default
 #endif
 
 static int fails = 0;
