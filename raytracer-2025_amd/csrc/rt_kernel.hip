@@ -172,6 +172,12 @@ struct Frame {
 // first bad ref) and read as index 0, so the run itself stays in bounds.
 // The product build compiles the check away.
 #ifdef RT_CHECK
+// The basic tier's slab guard (visit4_rows) reports through the same counter
+// under a kind no ref has: "kind 15, index <node>" in the host's message is
+// a node whose visit saw slab_f and slab_sorted_f differ, not a ref past its
+// array.
+constexpr uint32_t K_CHECK_SLAB = 15;
+static_assert(K_CHECK_SLAB > K_POPXF, "the slab guard's marker must not be a ref kind");
 __device__ unsigned long long g_check[2];
 __device__ __noinline__ void check_fail(uint32_t ref) {
     atomicAdd(&g_check[0], 1ull);
@@ -822,7 +828,26 @@ struct Trav {
     HitInfo hit;
     uint32_t nmed;  // FULL: media met by the walk, tested after it (media_phase)
     uint32_t pn;    // BASIC (4-wide): the number of spheres queued for the exact test
+    // BASIC: rf with each axis' two planes in the order the ray meets them
+    // (rt_slab.h RaySF), and per axis the byte offset from a node's lo row to
+    // its near row in the LDS copy -- 0, or 48 (the hi row) where 1/d <= 0.
+    // Members of every tier's Trav like pn and nmed: only the basic tier
+    // sets or reads them, and the other tiers' code is what it was without
+    // them.  RaySF needs the folded widening (the ray's own scaling is what
+    // orders the planes), so the kernel builds with RT_SLAB_FOLD = 1 only;
+    // RT_SLAB_FOLD = 0 remains a setting of the header's CPU property test.
+    static_assert(RT_SLAB_FOLD == 1, "the basic tier's sign-ordered slab test (RaySF) needs RT_SLAB_FOLD = 1");
+    RaySF sf;
+    uint32_t so[3];
 };
+// The basic tier's sign-ordered ray fields (T.rf is read by the check build's
+// guard only: visit4_rows)
+__device__ __forceinline__ void trace_sorted_fields(const Ray& wr, Trav<TIER_BASIC>& T) {
+    const double o[3] = {wr.o.x, wr.o.y, wr.o.z}, d[3] = {wr.d.x, wr.d.y, wr.d.z};
+    T.sf = make_raysf(o, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) T.so[k] = T.sf.pos[k] ? 0u : 3u * (uint32_t)sizeof(float4);
+}
 
 template <int TIER>
 __device__ __forceinline__ void trace_begin(const SceneView& S, const Ray& wr, Trav<TIER>& T) {
@@ -841,6 +866,7 @@ __device__ __forceinline__ void trace_begin(const SceneView& S, const Ray& wr, T
     if constexpr (TIER == TIER_BASIC) {
         T.pn = 0;
         T.cur = bword(S, S.world_root);  // the 4-wide walk's cur is a walk word
+        trace_sorted_fields(wr, T);
     }
 }
 
@@ -902,6 +928,7 @@ __device__ __forceinline__ void trace_unpark_state2(Trav<TIER_BASIC>& T, const R
 }
 __device__ __forceinline__ void trace_ray_fields(const Ray& wr, Trav<TIER_BASIC>& T) {
     T.rf = make_rayf(wr);
+    trace_sorted_fields(wr, T);
     T.a = len2(wr.d);
     T.inva = 1.0 / T.a;
 }
@@ -1224,14 +1251,41 @@ __device__ __forceinline__ Node4Rows load_node4(const RT_LDS float4* nl, uint32_
     const RT_LDS float4* np = nl + idx * 7u;
     return Node4Rows{np[0], np[1], np[2], np[3], np[4], np[5], np[6]};
 }
-// visit4 on node rows already loaded; the ref row holds walk words (bword)
+// The same node with each axis' rows in the order the lane's ray meets them
+// (Trav::so): the near row of axis k is row k + s and its far row 3 + k - s,
+// with s = 0 where 1/d > 0 and 3 otherwise -- an add on the node's address
+// per row, the row's constant in the read's offset field, and still seven
+// ds_read_b128.  The slab test then needs no min / max to pair an axis' two
+// plane distances (rt_slab.h slab_sorted_f): 6 VALU fewer a slot.
+struct Node4Sorted {
+    float4 nx, ny, nz, fx, fy, fz, rq;
+};
+__device__ __forceinline__ Node4Sorted load_node4_sorted(const RT_LDS float4* nl, uint32_t idx, const uint32_t so[3]) {
+    const RT_LDS char* np = (const RT_LDS char*)(nl + idx * 7u);
+    auto row = [](const RT_LDS char* p, int r) { return ((const RT_LDS float4*)p)[r]; };
+    return Node4Sorted{row(np + so[0], 0), row(np + so[1], 1), row(np + so[2], 2), row(np - so[0], 3),
+                       row(np - so[1], 4), row(np - so[2], 5), row(np, 6)};
+}
+// visit4 on node rows already loaded; the ref row holds walk words (bword).
+// The check build also gets the rows as stored (raw) and the unsorted ray
+// (rf), runs slab_f beside every slab_sorted_f and reports a differing
+// verdict, or a differing entry on a hit, through check_fail as index `node`
+// under the marker kind K_CHECK_SLAB: every render on the check library holds the two tests' agreement
+// as the GPU compiles them.
 template <class Stack>
-__device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4Rows& nr, const RayF& rf, float tmin_f,
-                                                float c_f, Stack& stk, uint32_t& sp, RT_LDS uint16_t* pq, uint32_t& pn) {
-    const float4 lx = nr.lx, ly = nr.ly, lz = nr.lz, hx = nr.hx, hy = nr.hy, hz = nr.hz, rq = nr.rq;
-    const float LX[4] = {lx.x, lx.y, lx.z, lx.w}, LY[4] = {ly.x, ly.y, ly.z, ly.w}, LZ[4] = {lz.x, lz.y, lz.z, lz.w};
-    const float HX[4] = {hx.x, hx.y, hx.z, hx.w}, HY[4] = {hy.x, hy.y, hy.z, hy.w}, HZ[4] = {hz.x, hz.y, hz.z, hz.w};
+__device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4Sorted& nr, const RaySF& sf,
+                                                float tmin_f, float c_f, Stack& stk, uint32_t& sp,
+                                                RT_LDS uint16_t* pq, uint32_t& pn, const Node4Rows& raw,
+                                                const RayF& rf, uint32_t node) {
+    const float4 nx = nr.nx, ny = nr.ny, nz = nr.nz, fx = nr.fx, fy = nr.fy, fz = nr.fz, rq = nr.rq;
+    const float NX[4] = {nx.x, nx.y, nx.z, nx.w}, NY[4] = {ny.x, ny.y, ny.z, ny.w}, NZ[4] = {nz.x, nz.y, nz.z, nz.w};
+    const float FX[4] = {fx.x, fx.y, fx.z, fx.w}, FY[4] = {fy.x, fy.y, fy.z, fy.w}, FZ[4] = {fz.x, fz.y, fz.z, fz.w};
     const uint32_t R[4] = {__float_as_uint(rq.x), __float_as_uint(rq.y), __float_as_uint(rq.z), __float_as_uint(rq.w)};
+#ifdef RT_CHECK
+    const float LX[4] = {raw.lx.x, raw.lx.y, raw.lx.z, raw.lx.w}, LY[4] = {raw.ly.x, raw.ly.y, raw.ly.z, raw.ly.w};
+    const float LZ[4] = {raw.lz.x, raw.lz.y, raw.lz.z, raw.lz.w}, HX[4] = {raw.hx.x, raw.hx.y, raw.hx.z, raw.hx.w};
+    const float HY[4] = {raw.hy.x, raw.hy.y, raw.hy.z, raw.hy.w}, HZ[4] = {raw.hz.x, raw.hz.y, raw.hz.z, raw.hz.w};
+#endif
     uint32_t w[4];
     // per slot, one slab test when some lane has a child there: a sphere
     // child's row holds its own box (rth::bvh4_convert), and a hit queues it
@@ -1248,9 +1302,17 @@ __device__ __forceinline__ uint32_t visit4_rows(const SceneView& S, const Node4R
         const bool any = R[i] != 0u, box = R[i] > 0xffffu, sph = any && !box;
         w[i] = SORT4_NONE;
         if (__ballot(any)) {
-            const float lo[3] = {LX[i], LY[i], LZ[i]}, hi[3] = {HX[i], HY[i], HZ[i]};
+            const float nr3[3] = {NX[i], NY[i], NZ[i]}, fr3[3] = {FX[i], FY[i], FZ[i]};
             float e;
-            const bool h = slab_f(lo, hi, rf, tmin_f, c_f, e);
+            const bool h = slab_sorted_f(nr3, fr3, sf, tmin_f, c_f, e);
+#ifdef RT_CHECK
+            {
+                const float lo[3] = {LX[i], LY[i], LZ[i]}, hi[3] = {HX[i], HY[i], HZ[i]};
+                float e0;
+                const bool h0 = slab_f(lo, hi, rf, tmin_f, c_f, e0);
+                if (any && (h0 != h || (h && __float_as_uint(e0) != __float_as_uint(e)))) check_fail(make_ref(K_CHECK_SLAB, node));
+            }
+#endif
             // The queue store is unconditional and only the count is not: a
             // lane that queues nothing writes above its queue's top, into an
             // entry nothing reads before the next push overwrites it.  That
@@ -1406,7 +1468,12 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
     // cur is a walk word (bword): a node, a list position or a sphere
     const uint32_t r16 = cur >> 16;
     const bool node = r16 - 1u < 0x7fffu;  // 1 ..= 0x7fff
-    const Node4Rows rows = load_node4(nl - 7, node ? r16 : 1u);
+    const Node4Sorted rows = load_node4_sorted(nl - 7, node ? r16 : 1u, T.so);
+#ifdef RT_CHECK
+    const Node4Rows raw = load_node4(nl - 7, node ? r16 : 1u);
+#else
+    const Node4Rows raw{};  // read by the check build only
+#endif
 
     if (__ballot(!node && cur != 0u)) {  // lists, standalone spheres (none in C2)
         if (r16 >= 0x8000u) {  // a list position
@@ -1424,7 +1491,7 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
     if (node) {
         RT_ISA_MARK("walk_visit");
         RT_DIAG_ONLY(++dg.node_visits;)
-        T.cur = visit4_rows(S, rows, T.rf, tmin_f, T.cl.c_f, stk, T.sp, pq, pn);
+        T.cur = visit4_rows(S, rows, T.sf, tmin_f, T.cl.c_f, stk, T.sp, pq, pn, raw, T.rf, r16 - 1u);
     }
     // the sphere round's f64 test after the node visit: the visit's LDS rows
     // arrive before the sphere's global load, and the test then finds it

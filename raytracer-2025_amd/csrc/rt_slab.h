@@ -2,7 +2,9 @@
 //
 // Host and device: the kernel (rt_kernel.hip) runs it, and the CPU property
 // test (tests/test_slab_cpu.py, tests/cpp/slab_prop.cpp) checks it against the
-// slab test of aabb.rs:62-78 evaluated in extended precision.
+// slab test of aabb.rs:62-78 evaluated in extended precision.  The basic
+// tier walks with the sign-ordered form of the same test (RaySF, slab_sorted_f
+// at the end of this file; tests/test_slab_sorted_cpu.py).
 //
 // aabb.rs:62-78: per axis t0 = (lo - o) / d, t1 = (hi - o) / d, the interval
 // [min, max] of the two intersected with the ray's [t_min, t_max]; a hit when
@@ -216,5 +218,74 @@ RT_HD bool slab_f(const float* lo, const float* hi, const RayF& R, float tmin_f,
     return entry <= fminf(fmaf(fabsf(fr), REL, fr), c_f);
 #endif
 }
+
+#if RT_SLAB_FOLD
+// The same test with the min / max pairing of an axis' two plane distances
+// done once per ray (the basic tier's visit4_rows): make_rayf already scales
+// the lo planes as the near ones where 1/d > 0 and the hi planes otherwise, so
+// the ray knows which plane of an axis it meets first.  RaySF holds the
+// coefficient pairs in that order and the caller hands the box's planes over
+// in it: near[k] = pos[k] ? lo[k] : hi[k], far[k] the other.  The six plane
+// distances are the very values slab_f computes.  Where an axis has near <=
+// far -- always, when the box is not wholly behind the origin on that axis --
+// slab_f's min / max return them as they stand and both tests give the same
+// entry and verdict.  Where rounding leaves near > far (both negative: the
+// slab lies behind the origin, and the two scalings move the planes apart the
+// other way), slab_f has exit <= max(near, far) < 0 < t_min <= entry and this
+// one entry >= near > far >= exit: both miss.  tests/test_slab_sorted_cpu.py
+// holds the agreement, bit for bit.
+struct RaySF {
+    float idn[3], nn[3];  // the near planes' coefficient pair (RayF's idl, nlo where pos)
+    float idf[3], nf[3];  // the far planes'
+    bool pos[3];          // 1/d > 0: the lo plane is the near one
+};
+
+// make_rayf's clamped 1/d of one axis, the same expression
+RT_HD float rayf_inv(double dk) {
+#if RT_RCP_F32 == 2
+    float f = rcp_f32((float)dk);
+#elif RT_RCP_F32
+    float f = 1.0f / (float)dk;
+#else
+    float f = (float)(1.0 / dk);
+#endif
+    if (!(fabsf(f) <= 1.152921504606847e18f)) f = copysignf(1.152921504606847e18f, f);
+    return f;
+}
+
+// make_rayf(o, d) with each axis' two pairs in the ray's order, by make_rayf's
+// own predicate f > 0: {idn, nn} = pos ? {idl, nlo} : {idh, nhi}, {idf, nf}
+// the other pair, bit for bit (tests/cpp/slab_sorted_prop.cpp compares them).
+// Written out, not selected from a RayF: the near plane's scale is 1 - 2^-21
+// and the far plane's 1 + 2^-21 whatever the sign, and only the pad changes
+// sides -- one select an axis where picking from make_rayf's result takes
+// four on top of make_rayf's two (which the compiler does not fold).
+RT_HD RaySF make_raysf(const double o[3], const double d[3]) {
+    RaySF Q;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float f = rayf_inv(d[k]);
+        const bool p = f > 0.0f;
+        const float of = (float)o[k];
+        const float pad = fabsf(of) * 4.76837158203125e-07f + 1e-30f;  // 2^-21 |o|
+        const float pn = p ? pad : -pad;  // the lo plane moves down, the hi plane up
+        constexpr float SHRINK = 1.0f - 4.76837158203125e-07f, GROW = 1.0f + 4.76837158203125e-07f;
+        Q.pos[k] = p;
+        Q.idn[k] = f * SHRINK;
+        Q.idf[k] = f * GROW;
+        Q.nn[k] = -((of + pn) * f) * SHRINK;
+        Q.nf[k] = -((of - pn) * f) * GROW;
+    }
+    return Q;
+}
+
+RT_HD bool slab_sorted_f(const float* near, const float* far, const RaySF& Q, float tmin_f, float c_f, float& entry) {
+    const float tnx = fmaf(near[0], Q.idn[0], Q.nn[0]), tfx = fmaf(far[0], Q.idf[0], Q.nf[0]);
+    const float tny = fmaf(near[1], Q.idn[1], Q.nn[1]), tfy = fmaf(far[1], Q.idf[1], Q.nf[1]);
+    const float tnz = fmaf(near[2], Q.idn[2], Q.nn[2]), tfz = fmaf(far[2], Q.idf[2], Q.nf[2]);
+    entry = fmaxf(fmaxf(fmaxf(tnx, tny), tnz), tmin_f);
+    return entry <= fminf(fminf(fminf(tfx, tfy), tfz), c_f);
+}
+#endif
 
 }  // namespace rtk
