@@ -1424,10 +1424,23 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
     // round and its sphere load issued first, ahead of the node's seven LDS
     // reads; its f64 test comes after the node visit, by when the load has
     // landed.
-    const bool can = (T.cur != 0u || T.sp > 0) && pn <= ROOM;
-    const unsigned long long mw0 = __ballot(can);
+    const bool has = T.cur != 0u || T.sp > 0;  // a word to walk, now or on the stack
+    const bool can = has && pn <= ROOM;
+    // (the AND of two ballots, each a compare into a scalar pair: the ballot
+    // of the AND goes through a 0 / 1 vector register and a second compare)
+    const unsigned long long mh0 = __ballot(has);
+    const unsigned long long mw0 = mh0 & __ballot(pn <= ROOM);
     const unsigned long long mp0 = __ballot(pn > 0);
-    const uint32_t in_walk = (uint32_t)__popcll(__ballot(true));
+    // The lanes in the walk are those with a word to walk or a sphere queued
+    // (what the last step returned true for, or a walk just begun): the
+    // batch loop calls the step with every lane of the wave, and a lane whose
+    // walk is over, or that has no path, holds the empty state -- it cannot
+    // walk, has no round, reads entry 0 like every lane without one, and
+    // returns false.  The count as a 32-bit scalar the compiler cannot see
+    // through: it otherwise widens the compare below to 64 bits, which only
+    // the vector unit has.
+    uint32_t in_walk = (uint32_t)__popcll(mh0 | mp0);
+    asm("" : "+s"(in_walk));
     const uint32_t thresh =
         in_walk <= RT_DEFER_THIN ? 1u : min((uint32_t)RT_DEFER_THRESH, (in_walk * 3u + 3u) / 4u);
     const bool round = (mw0 == 0 || (uint32_t)__popcll(mp0) >= thresh) && pn > 0;
@@ -1483,7 +1496,13 @@ __device__ __forceinline__ bool trace4_step(const SceneView& S, const Ray& r, Tr
                 if (S.list_children[li + 1] != REF_NONE) stk.push_w(T.sp++, (0x8000u | (li + 1)) << 16, NO_CULL);
                 T.cur = bword(S, child);
             }
-        } else {  // a sphere element of a list: queued for its exact test
+        } else if (r16 == 0u && cur != 0u) {  // a sphere element of a list: queued for its exact test
+            // (the lane's own word decides: the block is entered on the
+            // wave's ballot, and a lane at a node, or with no word at all --
+            // waiting for its round, or holding the empty state -- queues
+            // nothing here.  Until round 10 such a lane queued its word's
+            // low half, sphere 0: a test more that changed no hit, and for a
+            // lane at a node a fifth entry ahead of the visit's four.)
             pq[pn * RT_BLOCK_BASIC] = (uint16_t)cur;
             ++pn;
         }
@@ -2577,7 +2596,9 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                 // the state is then defined on every path into the walk, so
                 // that the compiler need not keep the last walk's values live
                 // through the shading code (C2 -1.6 %: 28 B/lane of scratch
-                // -> none, 128 -> 124 VGPRs; ab_define_t_c2_128spp.json)
+                // -> none, 128 -> 124 VGPRs; ab_define_t_c2_128spp.json).
+                // Its state is the empty one -- no word to walk, nothing
+                // queued: the walk loop below steps every lane of the wave
                 trace_ray_fields(ray, T);
                 if (!walking) {
                     T.cl.c = __builtin_huge_val();
@@ -2588,7 +2609,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                     T.nxf = 0;
                     T.hit.nxf = 0;
                     T.nmed = 0;
-                    T.cur = bword(S, S.world_root);
+                    T.cur = no_path ? 0u : bword(S, S.world_root);
                     if (!no_path) {
                         rng.begin(vertex);
                         ++n_rays;
@@ -2615,12 +2636,23 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                 while (walking) walking = step();
 #endif
             } else {
+                // Every lane of the wave takes the step, in uniform control
+                // flow: a lane that is not walking holds the empty state, on
+                // which a step does nothing and returns false.  The step's
+                // verdict is then a compare of every lane, and its ballot the
+                // compare's own mask -- under `if (walking)` the verdict was
+                // merged into the lanes' mask, and the ballot went through a
+                // 0 / 1 vector register and a second compare at every step
+                // (C2 -2.0 %, profiles/r10/ab_walk_rounds_c2_128spp.json).
                 const unsigned long long active = __ballot(true);
-                for (;;) {
-                    if (walking) walking = step();
-                    const unsigned long long w = __ballot(walking);
-                    if (w == 0 || __popcll(active & ~w) >= BATCH) break;
-                }
+                if (__ballot(walking))
+                    for (;;) {
+                        walking = step();
+                        const unsigned long long w = __ballot(walking);
+                        uint32_t done = (uint32_t)__popcll(active & ~w);
+                        asm("" : "+s"(done));  // (a 32-bit scalar compare: see trace4_step's in_walk)
+                        if (w == 0 || done >= (uint32_t)BATCH) break;
+                    }
             }
             RT_DIAG_ONLY(const unsigned long long t_b1 = __builtin_amdgcn_s_memtime(); dg.cyc_trace += t_b1 - t_b0;)
             // a walk that carries over this shading round is parked;
