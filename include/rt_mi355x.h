@@ -236,6 +236,60 @@ typedef struct rt_world_info {
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, uint32_t flags,
                           rt_world_info* out);
 
+/* ---- Hit queries: Hittable::hit (src/hit.rs:46-60) ------------------------- */
+/* One query ray.  The direction is used as given (not normalised); t_max is
+ * the interval's upper end and may be +inf. */
+typedef struct rt_ray {
+    double origin[3];
+    double dir[3];
+    double time;
+    double t_max;
+} rt_ray; /* 64 B */
+/* HitRecord (hit.rs:11-43) as hit() returns it: p, the unit normal turned
+ * against the ray, the primitive's own (u, v) -- for an OBJ triangle the
+ * record before RemappedMaterial::remap_record (obj.rs:32-62), which belongs
+ * to the material -- and mat, the index in the flattened material table (the
+ * rt_mat_* handle of a material the caller made).  A ConstantMedium hit has
+ * RT_HIT_MEDIUM, u = v = 0 and the normal (1, 0, 0) of volume.rs:67-72, which
+ * HitRecord::new turns against the ray like any other: (-1, -0, -0) where
+ * dir.x >= 0; its mat is the medium's own Isotropic, a slot of the table
+ * that no caller's handle names.  A miss has flags 0, mat -1 and every
+ * double 0. */
+typedef struct rt_hit_record {
+    double t;
+    double p[3];
+    double normal[3];
+    double u, v;
+    int32_t mat;
+    uint32_t flags; /* RT_HIT_* */
+} rt_hit_record;    /* 80 B */
+#define RT_HIT_FOUND 1u
+#define RT_HIT_FRONT_FACE 2u
+#define RT_HIT_MEDIUM 4u
+/* world.hit(Ray{origin, dir, time}, [1e-8, t_max]) (camera.rs:286 with the
+ * caller's upper end; both ends inclusive, interval.rs:65-67) for each of n
+ * rays, from host arrays into host arrays on the calling thread's current
+ * device.  Blocking.  A ConstantMedium's one draw per test (volume.rs:58) is
+ * the RNG contract's medium stream (oracle/rng_contract.hpp) of key `seed`,
+ * pixel = the ray's index, sample 0, vertex 1 -- hence n < 2^32.  flags:
+ * RT_FLAG_REFERENCE_BVH or 0.  The world is flattened and uploaded as for
+ * rt_render(world, lights = -1, background = -1, flags) and shares the
+ * scene's per-device world cache; the device work is ordered after the
+ * scene's previous device work, as renders are.
+ * RT_EINVAL: a null scene; a null array with n > 0; n >= 2^32; unknown flags;
+ * a ray with a non-finite origin, direction or time, a zero direction, or a
+ * NaN or negative t_max.  RT_EHANDLE / RT_EMOVED as rt_render.  RT_EDEVICE
+ * without a gfx950 device (there is no CPU fallback).  n == 0 is RT_OK,
+ * touches no device and needs no arrays. */
+int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                     rt_hit_record* out);
+/* The same from and to gfx950 device arrays, enqueued on `stream` (a
+ * hipStream_t; NULL = the default stream) without waiting.  The rays cannot be
+ * validated here: they are the caller's duty, and the kernel ends and writes a
+ * record for any ray. */
+int32_t rt_world_hit_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_device,
+                            uint64_t n, rt_hit_record* out_device, void* stream);
+
 /* Number of rows a shard renders (rows of the compact output). */
 uint32_t rt_shard_rows(const rt_camera* cam, const rt_render_opts* opts);
 

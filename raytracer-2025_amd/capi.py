@@ -73,6 +73,33 @@ class RtStats(C.Structure):
     ]
 
 
+class RtRay(C.Structure):
+    """rt_ray -- one query ray of rt_world_hit (64 B)."""
+
+    _fields_ = [
+        ("origin", c_double3),
+        ("dir", c_double3),
+        ("time", C.c_double),
+        ("t_max", C.c_double),
+    ]
+
+
+class RtHitRecord(C.Structure):
+    """rt_hit_record -- HitRecord (hit.rs:11-43) of one query ray (80 B)."""
+
+    _fields_ = [
+        ("t", C.c_double),
+        ("p", c_double3),
+        ("normal", c_double3),
+        ("u", C.c_double),
+        ("v", C.c_double),
+        ("mat", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+HIT_FOUND, HIT_FRONT_FACE, HIT_MEDIUM = 1, 2, 4
+
 _P = C.c_void_p
 _I = C.c_int32
 _U = C.c_uint32
@@ -118,6 +145,8 @@ SIGNATURES = {
     "render_opts_default": (None, [C.POINTER(RtRenderOpts)]),
     "render": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.POINTER(C.c_float),
                     C.POINTER(C.c_uint8), C.POINTER(RtStats)]),
+    "world_hit": (_I, [_P, _I, C.c_uint64, _U, C.POINTER(RtRay), C.c_uint64, C.POINTER(RtHitRecord)]),
+    "world_hit_device": (_I, [_P, _I, C.c_uint64, _U, _P, C.c_uint64, _P, _P]),
     "shard_rows": (_U, [C.POINTER(RtCamera), C.POINTER(RtRenderOpts)]),
     "render_device": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), _P]),
     "render_device_wait": (_I, [_P, C.POINTER(RtStats)]),
@@ -138,7 +167,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -141,6 +141,15 @@ extern "C" hipError_t rtk_launch_math(int fn, int impl, const double* a, const d
 // the f32 walk stages, from device arrays.
 extern "C" int rtk_walk_widths(int fn, int* in_w, int* out_w);
 extern "C" hipError_t rtk_launch_walk(int fn, const double* in, double* out, uint64_t n, hipStream_t stream);
+// rt_world_hit's kernel: world.hit of n rays (device arrays) on the tier's
+// walk, records to out; grid <= the tier's path-kernel grid (stack_ovf is sized
+// for it).  Weak: the launcher links without the kernels in its CPU test
+// (tests/cpp/hip_stub.cpp), where rt_world_hit reports RT_EUNSUPPORTED.
+struct rt_ray;
+struct rt_hit_record;
+extern "C" __attribute__((weak)) hipError_t rtk_launch_hits(const rtk::SceneView* view, const struct rt_ray* rays,
+                                                            struct rt_hit_record* out, uint64_t n, uint64_t seed,
+                                                            int tier, int grid, void* stack_ovf, hipStream_t stream);
 // device bytes rtk_launch_frame needs at params_dev
 extern "C" size_t rtk_params_bytes(void);
 extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu);

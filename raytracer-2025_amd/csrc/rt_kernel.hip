@@ -19,6 +19,7 @@
 // in LDS, laid out [depth][lane] so a wave's pushes/pops hit 64 distinct banks.
 #include <hip/hip_runtime.h>
 
+#include "../../include/rt_mi355x.h"
 #include "rt_crmath.h"
 #include "rt_kernel.h"
 #include "rt_math.h"
@@ -1545,7 +1546,11 @@ struct Rec {
 
 // HitRecord::new (hit.rs:24-43) of the recorded closest hit, in the frame of
 // its innermost Transform, then carried out through the chain (shapes.rs:104-108).
-template <int TIER>
+// QUERY (rt_hit_kernel): the record as Hittable::hit returns it -- the
+// primitive's own (u, v) always, whether or not a texture reads them, and an
+// OBJ triangle's record before RemappedMaterial::remap_record, which is the
+// material's work (obj.rs:32-62), not hit's.
+template <int TIER, bool QUERY = false>
 __device__ Rec make_record(const SceneView& S, const Ray& wr, const HitInfo& h, bool& panic) {
     constexpr bool FULL = tier_full(TIER), PLANAR = TIER >= TIER_MESH;
     Ray r = wr;
@@ -1574,7 +1579,7 @@ __device__ Rec make_record(const SceneView& S, const Ray& wr, const HitInfo& h, 
             rec.mat = S.msph_mat[idx];
         }
         outward = rinv * (p - c);
-        if (S.materials[rec.mat].flags & MF_NEEDS_UV) {
+        if (QUERY || (S.materials[rec.mat].flags & MF_NEEDS_UV)) {
             // sphere.rs:53-61
             const double theta = k_acos(-outward.y);
             const double phi = k_atan2(-outward.z, outward.x) + PI;
@@ -1589,7 +1594,7 @@ __device__ Rec make_record(const SceneView& S, const Ray& wr, const HitInfo& h, 
         // them or an OBJ triangle's RemappedMaterial (obj.rs:32-62); nothing
         // else looks at them (full tiers: C3 -1.3 %, C5 -2 %; the mesh tier's
         // OBJ triangles always need them)
-        if (!FULL || (S.materials[rec.mat].flags & MF_NEEDS_UV) ||
+        if (QUERY || !FULL || (S.materials[rec.mat].flags & MF_NEEDS_UV) ||
             (PLANAR && kind == K_TRI && S.planar_remap[idx] >= 0)) {
             const D3 hv = p - d3(P.f[4], P.f[5], P.f[6]);
             const D3 u = d3(P.f[7], P.f[8], P.f[9]), v = d3(P.f[10], P.f[11], P.f[12]), w = d3(P.f[13], P.f[14], P.f[15]);
@@ -1611,7 +1616,7 @@ __device__ Rec make_record(const SceneView& S, const Ray& wr, const HitInfo& h, 
             rec.n = unit(quat_rotate(X.q[0], X.q[1], X.q[2], X.q[3], rec.n / d3(X.scale[0], X.scale[1], X.scale[2])), ok);
         }
     }
-    if constexpr (PLANAR) {
+    if constexpr (PLANAR && !QUERY) {
         // RemappedMaterial::remap_record (obj.rs:32-62), no normal map: applied to
         // the record every material of an OBJ triangle sees (scatter and emitted)
         if (kind == K_TRI) {
@@ -2333,6 +2338,62 @@ __device__ __forceinline__ StackFor<TIER> make_stack(RT_LDS uint2* s8, RT_LDS ui
         return StackFor<TIER>{s8, ovf, stride};
 }
 constexpr uint32_t RT_PARK_WORDS = 8;
+// The LDS set-up every kernel over the walk makes before its first ray
+// (rt_path_kernel, rt_hit_kernel).  The lane arena (all tiers but the basic
+// one) is one uint2 row per lane and row, RT_BLOCK apart: the stack's rows
+// first, then (full tiers) the media queue's -- lane_rows_med is where those
+// start; make_stack (above) binds a lane's stack to its rows and to its
+// column of the global overflow buffer.
+template <int TIER>
+constexpr uint32_t lane_rows_med() {
+    return TIER == TIER_BASIC ? 0u : lds_stack_entries(TIER);
+}
+// A lane's views of the block's walk arrays: its arena row, the media queue in
+// it, its sphere queue and its stack.  The arrays themselves are each
+// kernel's own (their sizes depend on what else the kernel parks in LDS).
+template <int TIER>
+struct WalkLds {
+    RT_LDS uint2* lrow;
+    MedQ med;
+    RT_LDS uint16_t* pq;
+    StackFor<TIER> stk;
+};
+template <int TIER>
+__device__ __forceinline__ WalkLds<TIER> walk_lds(uint2* lane_lds, uint32_t* stack4_lds, uint16_t* pend_lds,
+                                                  RT_GLOBAL uint2* stack_ovf) {
+    constexpr uint32_t BLK = TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK;
+    RT_LDS uint2* const lrow = (RT_LDS uint2*)(lane_lds + threadIdx.x);
+    return WalkLds<TIER>{lrow, MedQ{lrow + lane_rows_med<TIER>() * BLK}, (RT_LDS uint16_t*)(pend_lds + threadIdx.x),
+                         make_stack<TIER>(lrow, (RT_LDS uint32_t*)(stack4_lds + threadIdx.x),
+                                          stack_ovf + (uint64_t)blockIdx.x * BLK + threadIdx.x, gridDim.x * BLK)};
+}
+// Basic tier: the block's copy of the world's 4-wide nodes (at most CAP: the
+// launcher gives the tier no larger tree), the ref rows as walk words (bword);
+// ends on the block's barrier.  A macro, unlike walk_lds above: as a
+// __forceinline__ function template (node_lds as a pointer or as an array
+// reference) the loop compiles differently in rt_path_kernel<TIER_BASIC> --
+// the LDS store's address runs from 0x12000 up, not from 0x12008 with an
+// offset of -8, the kernel is two instructions shorter (7 496 lines of
+// llvm-objdump -d for 7 498) and every later address moves -- and the path
+// kernels' code objects were to stay byte for byte what they were when the
+// hit kernels came in.  walk_lds leaves all five identical.  The next change
+// that re-measures the basic tier anyway can make this a function.
+#define RT_COPY_NODES_LDS(S, node_lds, CAP, BLK)                                                      \
+    do {                                                                                              \
+        const uint32_t n_lds = min((S).n_nodes4, (CAP)); /* == n_nodes4 (launcher) */                 \
+        const RT_GLOBAL float4* src = reinterpret_cast<const RT_GLOBAL float4*>((S).nodes4);          \
+        for (uint32_t k = threadIdx.x; k < n_lds * 7u; k += (BLK)) {                                  \
+            float4 v = src[k];                                                                        \
+            if (k % 7u == 6u) { /* the ref row: walk words (bword) */                                 \
+                v.x = __uint_as_float(bword((S), __float_as_uint(v.x)));                              \
+                v.y = __uint_as_float(bword((S), __float_as_uint(v.y)));                              \
+                v.z = __uint_as_float(bword((S), __float_as_uint(v.z)));                              \
+                v.w = __uint_as_float(bword((S), __float_as_uint(v.w)));                              \
+            }                                                                                         \
+            (node_lds)[k] = v;                                                                        \
+        }                                                                                             \
+        __syncthreads();                                                                              \
+    } while (0)
 
 // WIDE (basic tier only): the variant for trees of NODE_LDS_CAP_BATCH +
 // 1 .. NODE_LDS_CAP nodes -- the whole LDS node copy, whole-wave shading, no
@@ -2358,18 +2419,18 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     // array held across the path loop
     constexpr bool LDS_STATE = TIER == TIER_FULL_FLAT;
     constexpr bool PARK_RAY = LDS_STATE;  // + the world ray (7 doubles)
-    constexpr uint32_t R_MED = B4 ? 0u : (uint32_t)STACK;
+    constexpr uint32_t R_MED = lane_rows_med<TIER>();
     constexpr uint32_t R_PST = R_MED + (tier_full(TIER) ? 2u * RT_MEDIA_CAP : 0u);
     constexpr uint32_t R_PIT = R_PST + (LDS_STATE ? (PARK_RAY ? 16u : 9u) : 0u);
     constexpr uint32_t R_END = R_PIT + (LDS_STATE ? 2u : 0u);
     __shared__ uint2 lane_lds[B4 ? 1 : R_END * BLK];
     __shared__ uint32_t stack4_lds[B4 ? STACK * BLK : 1];
-    RT_LDS uint2* const lrow = (RT_LDS uint2*)(lane_lds + threadIdx.x);
-    const MedQ med{lrow + R_MED * BLK};
     __shared__ uint16_t pend_lds[B4 ? RT_PEND_CAP * BLK : 1];
-    RT_LDS uint16_t* pq = (RT_LDS uint16_t*)(pend_lds + threadIdx.x);
-    StackFor<TIER> stk = make_stack<TIER>(lrow, (RT_LDS uint32_t*)(stack4_lds + threadIdx.x),
-                                          P->stack_ovf + (uint64_t)blockIdx.x * BLK + threadIdx.x, gridDim.x * BLK);
+    const WalkLds<TIER> wl = walk_lds<TIER>(lane_lds, stack4_lds, pend_lds, P->stack_ovf);
+    RT_LDS uint2* const lrow = wl.lrow;
+    const MedQ med = wl.med;
+    RT_LDS uint16_t* pq = wl.pq;
+    StackFor<TIER> stk = wl.stk;
     // Basic tier with shading batches: the walk state of a lane whose walk
     // carries over a shading round is parked here across it (RT_PARK_WORDS
     // words: cur, sp | pn | found, c, c_f, hit t, hit ref), so that the
@@ -2382,21 +2443,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     // Basic tier: the block's copy of the world's 4-wide nodes (the whole tree:
     // 241 nodes for C1/C2), read by every node visit instead of global memory.
     __shared__ float4 node_lds[B4 ? NODE_CAP * 7 : 1];
-    if constexpr (B4) {
-        const uint32_t n_lds = min(S.n_nodes4, NODE_CAP);  // == n_nodes4 (launcher: rtk_launch_frame)
-        const RT_GLOBAL float4* src = reinterpret_cast<const RT_GLOBAL float4*>(S.nodes4);
-        for (uint32_t k = threadIdx.x; k < n_lds * 7u; k += BLK) {
-            float4 v = src[k];
-            if (k % 7u == 6u) {  // the ref row: walk words (bword)
-                v.x = __uint_as_float(bword(S, __float_as_uint(v.x)));
-                v.y = __uint_as_float(bword(S, __float_as_uint(v.y)));
-                v.z = __uint_as_float(bword(S, __float_as_uint(v.z)));
-                v.w = __uint_as_float(bword(S, __float_as_uint(v.w)));
-            }
-            node_lds[k] = v;
-        }
-        __syncthreads();
-    }
+    if constexpr (B4) RT_COPY_NODES_LDS(S, node_lds, NODE_CAP, BLK);
     if constexpr (tier_full_bvh(TIER)) {
         if (S.n_perlin > 0) {
             const RT_GLOBAL float4* src = reinterpret_cast<const RT_GLOBAL float4*>(S.perlin);
@@ -3065,14 +3112,117 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     }
 }
 
+// ------------------------------------------------------------------ hit queries
+// rt_world_hit: world.hit(Ray{origin, dir, time}, [1e-8, t_max]) (hit.rs:46-60)
+// for n caller-given rays, one ray per lane, and the HitRecord each returns
+// (hit.rs:24-43) -- the path kernels' walk and record, called as they call
+// them: trace_begin, trace4_step (basic tier) or trace_step and media_phase,
+// then make_record in its query mode.  t_max enters as the walk's initial
+// closest bound with nothing found, so a hit at exactly t_max is accepted
+// (interval.rs:65-67) and one past it is not.  A ConstantMedium's draw is the
+// contract's medium stream of (seed, pixel = the ray's index, sample 0,
+// vertex 1).
+struct HitParams {
+    SceneView S;
+    const rt_ray* rays;
+    rt_hit_record* out;
+    uint64_t n;  // < 2^32 (the host's check): a ray's index is its Rng pixel
+    uint32_t key0, key1;
+    RT_GLOBAL uint2* stack_ovf;  // mesh / full tiers: [stack_need - LDS entries][grid * RT_BLOCK]
+};
+
+template <int TIER>
+__global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK) rt_hit_kernel(const HitParams P) {
+    const SceneView& S = P.S;
+    constexpr int STACK = lds_stack_entries(TIER);
+    constexpr uint32_t BLK = TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK;
+    constexpr bool B4 = TIER == TIER_BASIC;
+    // the path kernel's LDS set-up without its parked path state: the lane
+    // arena (stack rows, then the full tiers' media queue), or the basic
+    // tier's 4-B stack, sphere queue and whole node copy (as its WIDE variant)
+    constexpr uint32_t R_MED = lane_rows_med<TIER>();
+    constexpr uint32_t R_END = R_MED + (tier_full(TIER) ? 2u * RT_MEDIA_CAP : 0u);
+    __shared__ uint2 lane_lds[B4 ? 1 : R_END * BLK];
+    __shared__ uint32_t stack4_lds[B4 ? STACK * BLK : 1];
+    __shared__ uint16_t pend_lds[B4 ? RT_PEND_CAP * BLK : 1];
+    __shared__ float4 node_lds[B4 ? NODE_LDS_CAP * 7 : 1];
+    const WalkLds<TIER> wl = walk_lds<TIER>(lane_lds, stack4_lds, pend_lds, P.stack_ovf);
+    const MedQ med = wl.med;
+    RT_LDS uint16_t* pq = wl.pq;
+    StackFor<TIER> stk = wl.stk;
+    if constexpr (B4) RT_COPY_NODES_LDS(S, node_lds, NODE_LDS_CAP, BLK);
+    Diag dg;
+    Rng rng;
+    rng.k0 = P.key0;
+    rng.k1 = P.key1;
+    rng.sample = 0;
+    // Grid-stride over the rays, a wave at a time: the loop's bound is the
+    // wave's first ray, so the 64 lanes of a wave make the same trips and the
+    // lanes past n come along with no ray (the last wave only).
+    const uint64_t stride = (uint64_t)gridDim.x * BLK;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * BLK + (threadIdx.x & ~63u); w0 < P.n; w0 += stride) {
+        const uint64_t i = w0 + (threadIdx.x & 63u);
+        const bool live = i < P.n;
+        Ray ray{};
+        double t_max = 0.0;
+        if (live) {
+            const rt_ray q = P.rays[i];
+            ray.o = d3(q.origin[0], q.origin[1], q.origin[2]);
+            ray.d = d3(q.dir[0], q.dir[1], q.dir[2]);
+            ray.time = q.time;
+            t_max = q.t_max;
+        }
+        rng.pixel = (uint32_t)i;
+        rng.begin(1);
+        Trav<TIER> T;
+        trace_begin<TIER>(S, ray, T);
+        T.cl.set(t_max);
+        if constexpr (B4) {
+            // A lane with no ray holds the empty walk state (no word to walk,
+            // nothing queued: rt_path_kernel).  trace4_step ballots across
+            // the wave, so it is called in wave-uniform control flow, as the
+            // path kernel's batch loop calls it: every lane of the wave takes
+            // every step until none walks any more, and a step on a finished
+            // or empty walk does nothing and returns false.
+            if (!live) T.cur = 0u;
+            bool walking = live;
+            while (__ballot(walking))
+                walking = trace4_step(S, ray, T, stk, pq, (const RT_LDS float4*)node_lds, dg);
+        } else if (live) {
+            // (trace_step holds no cross-lane operation: each lane walks on its own)
+            while (trace_step<TIER>(S, ray, T, stk, rng, med, dg)) {
+            }
+            if constexpr (tier_full(TIER)) media_phase<TIER>(S, ray, T, stk, rng, med);
+        }
+        if (live) {
+            rt_hit_record o{};  // a miss: flags 0, mat -1, every double 0
+            o.mat = -1;
+            if (T.found) {
+                bool panic = false;  // (remap_record's unwraps: not reached in query mode)
+                const Rec rec = make_record<TIER, true>(S, ray, T.hit, panic);
+                o.t = T.hit.t;
+                o.p[0] = rec.p.x, o.p[1] = rec.p.y, o.p[2] = rec.p.z;
+                o.normal[0] = rec.n.x, o.normal[1] = rec.n.y, o.normal[2] = rec.n.z;
+                o.u = rec.u;
+                o.v = rec.v;
+                o.mat = rec.mat;
+                o.flags = RT_HIT_FOUND | (rec.front ? RT_HIT_FRONT_FACE : 0u) |
+                          (ref_kind(T.hit.ref) == K_MEDIUM ? RT_HIT_MEDIUM : 0u);
+            }
+            P.out[i] = o;
+        }
+    }
+}
+
 
 }  // namespace rtk
 
 // ------------------------------------------------------------------ host launchers
 // The product library compiles this file once per kernel tier (-DRT_TIER_ONLY=N,
 // each with its own code-generation flags, raytracer-2025_amd/Makefile) plus
-// once for the common part (-DRT_COMMON_ONLY); diagnostic / A-B builds compile
-// it whole.
+// once for the common part (-DRT_COMMON_ONLY) and once for the hit-query
+// kernels (-DRT_HIT_ONLY: no path-kernel object sees a second caller of the
+// walk or of make_record); diagnostic / A-B / check builds compile it whole.
 #define RT_TIER_ENTRY(N)                                                                                        \
     extern "C" hipError_t rtk_launch_path_##N(int grid, hipStream_t stream, const rtk::KParams* P) {          \
         hipLaunchKernelGGL(rtk::rt_path_kernel<N>, dim3(grid), dim3(N == 0 ? RT_BLOCK_BASIC : RT_BLOCK), 0, stream, P); \
@@ -3082,7 +3232,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, rtk::rt_path_kernel<N>,            \
                                                                  N == 0 ? RT_BLOCK_BASIC : RT_BLOCK, 0);         \
     }
-#if !defined(RT_COMMON_ONLY)
+#if !defined(RT_COMMON_ONLY) && !defined(RT_HIT_ONLY)
 #if !defined(RT_TIER_ONLY) || RT_TIER_ONLY == 0
 RT_TIER_ENTRY(0)
 // the basic tier's wide variant (trees past NODE_LDS_CAP_BATCH nodes)
@@ -3142,7 +3292,36 @@ extern "C" int rt_diag_counters(unsigned long long* out, int reset) {
 #endif
 #endif
 
-#if !defined(RT_TIER_ONLY)
+#if defined(RT_HIT_ONLY) || (!defined(RT_TIER_ONLY) && !defined(RT_COMMON_ONLY))
+// n rays through world.hit (rt_world_hit): rays and out are device arrays;
+// grid blocks of the tier's block size, at most the path kernel's grid --
+// stack_ovf is sized for that many lanes (rt_render.cpp upload_world).
+extern "C" hipError_t rtk_launch_hits(const rtk::SceneView* view, const rt_ray* rays, rt_hit_record* out, uint64_t n,
+                                      uint64_t seed, int tier, int grid, void* stack_ovf, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    rtk::HitParams P;
+    P.S = *view;
+    P.rays = rays;
+    P.out = out;
+    P.n = n;
+    P.key0 = (uint32_t)seed;
+    P.key1 = (uint32_t)(seed >> 32);
+    P.stack_ovf = (RT_GLOBAL uint2*)stack_ovf;
+    const int block = tier == rtk::TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK;
+    const uint64_t blocks = (n + (uint64_t)block - 1) / (uint64_t)block;
+    const dim3 g((unsigned)(blocks < (uint64_t)grid ? blocks : (uint64_t)grid)), b((unsigned)block);
+    switch (tier) {
+        case rtk::TIER_BASIC: hipLaunchKernelGGL(rtk::rt_hit_kernel<rtk::TIER_BASIC>, g, b, 0, stream, P); break;
+        case rtk::TIER_MESH: hipLaunchKernelGGL(rtk::rt_hit_kernel<rtk::TIER_MESH>, g, b, 0, stream, P); break;
+        case rtk::TIER_FULL: hipLaunchKernelGGL(rtk::rt_hit_kernel<rtk::TIER_FULL>, g, b, 0, stream, P); break;
+        case rtk::TIER_FULL_FLAT: hipLaunchKernelGGL(rtk::rt_hit_kernel<rtk::TIER_FULL_FLAT>, g, b, 0, stream, P); break;
+        default: return hipErrorInvalidValue;  // (lights = -1: no world selects TIER_FULL_GL)
+    }
+    return hipGetLastError();
+}
+#endif
+
+#if !defined(RT_TIER_ONLY) && !defined(RT_HIT_ONLY)
 extern "C" hipError_t rtk_launch_path_0(int, hipStream_t, const rtk::KParams*);
 extern "C" hipError_t rtk_launch_path_0w(int, hipStream_t, const rtk::KParams*);
 extern "C" hipError_t rtk_launch_path_1(int, hipStream_t, const rtk::KParams*);
@@ -3594,4 +3773,4 @@ extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu) {
          : tier == rtk::TIER_FULL_FLAT ? rtk_occupancy_3(blocks_per_cu)
                                        : rtk_occupancy_4(blocks_per_cu);
 }
-#endif  // !RT_TIER_ONLY
+#endif  // !RT_TIER_ONLY && !RT_HIT_ONLY

@@ -1065,6 +1065,108 @@ int32_t rt_render_device(rt_scene* s, int32_t world, int32_t lights, const rt_ca
     }
 }
 
+// rt_world_hit's argument checks, shared by both variants; n == 0 is decided
+// by the caller after them
+static int32_t hit_args(rt_scene* s, int32_t world, uint32_t flags, const void* rays, uint64_t n, const void* out) {
+    if (!s) return set_error(RT_EINVAL, "null scene");
+    if (flags & ~RT_FLAG_REFERENCE_BVH) return set_error(RT_EINVAL, "unknown flags");
+    if (n >= (1ull << 32)) return set_error(RT_EINVAL, "n must be below 2^32 (a ray's index is its RNG pixel)");
+    if (world < 0 || (size_t)world >= s->objs.size() || s->objs[world].hidden)
+        return set_error(RT_EHANDLE, "unknown world handle");
+    if (s->objs[world].moved) return set_error(RT_EMOVED, "world handle was moved");
+    if (n && (!rays || !out)) return set_error(RT_EINVAL, "null ray or record array");
+    return RT_OK;
+}
+
+// Enqueues the query on `stream` of the current device: slot 0's device world
+// as a render of (world, no lights, no background) leaves it, after the
+// slot's previous work.
+static int32_t hit_enqueue(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
+                           uint64_t n, rt_hit_record* out_dev, hipStream_t stream) {
+    int cur = -1;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
+    if (!rtk_launch_hits) return set_error(RT_EUNSUPPORTED, "this build holds no hit-query kernels");
+    if (!s->rs) s->rs = new RenderState();
+    RenderState* r = s->rs;
+    if (r->slots.empty()) r->slots.resize(1, nullptr);
+    // a slot on another device is made anew, and the last render's state on
+    // it (rt_render_device_wait) goes with it
+    if (r->slots[0] && r->slots[0]->device != cur) r->n_parts = 0;
+    DeviceWorld* d = nullptr;
+    int32_t rc = slot_for(r, 0, cur, d);
+    if (rc != RT_OK) return rc;
+    FlatWorld fw;
+    double flatten_ms = 0;
+    if ((rc = upload_world(s, d, world, -1, -1, (flags & RT_FLAG_REFERENCE_BVH) != 0, fw, flatten_ms)) != RT_OK)
+        return rc;
+    if (d->done_recorded && (e = hipStreamWaitEvent(stream, d->ev_done, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    if (r->g_recorded && (e = hipStreamWaitEvent(stream, r->g_stop, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    if ((e = rtk_launch_hits(&d->view, rays_dev, out_dev, n, seed, d->tier, d->grid[d->tier], d->stack_ovf, stream)) !=
+        hipSuccess)
+        return hip_fail(e, "hit kernel launch");
+    if ((e = hipEventRecord(d->ev_done, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    d->done_recorded = true;
+    return RT_OK;
+}
+
+int32_t rt_world_hit_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
+                            uint64_t n, rt_hit_record* out_dev, void* stream) {
+    const int32_t rc = hit_args(s, world, flags, rays_dev, n, out_dev);
+    if (rc != RT_OK || n == 0) return rc;
+    try {
+        return hit_enqueue(s, world, seed, flags, rays_dev, n, out_dev, (hipStream_t)stream);
+    } catch (const std::bad_alloc&) {
+        return set_error(RT_ENOMEM, "out of host memory");
+    }
+}
+
+int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                     rt_hit_record* out) {
+    int32_t rc = hit_args(s, world, flags, rays, n, out);
+    if (rc != RT_OK || n == 0) return rc;
+    for (uint64_t i = 0; i < n; ++i) {
+        const rt_ray& q = rays[i];
+        bool ok = std::isfinite(q.time) && q.t_max >= 0.0;  // (a NaN t_max fails the compare)
+        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(q.origin[k]) && std::isfinite(q.dir[k]);
+        ok = ok && (q.dir[0] != 0.0 || q.dir[1] != 0.0 || q.dir[2] != 0.0);
+        if (!ok)
+            return set_error(RT_EINVAL, "ray " + std::to_string(i) +
+                                            ": non-finite origin, direction or time, zero direction, or NaN / negative t_max");
+    }
+    char* buf = nullptr;
+    const size_t ray_bytes = (size_t)n * sizeof(rt_ray), out_bytes = (size_t)n * sizeof(rt_hit_record);
+    hipError_t e = hipMalloc((void**)&buf, ray_bytes + out_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc rays");
+    rt_hit_record* out_dev = (rt_hit_record*)(buf + ray_bytes);
+    if ((e = hipMemcpy(buf, rays, ray_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        rc = hip_fail(e, "hipMemcpy rays");
+    } else {
+        try {
+            rc = hit_enqueue(s, world, seed, flags, (const rt_ray*)buf, n, out_dev, nullptr);
+        } catch (const std::bad_alloc&) {
+            rc = set_error(RT_ENOMEM, "out of host memory");
+        }
+        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "hit query (stream synchronize)");
+        if (rc == RT_OK && (e = hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = hip_fail(e, "hipMemcpy records");
+        if (rc == RT_OK && rtk_check_read) {  // check build: refs past their arrays, as a render reports them
+            unsigned long long c[2] = {0, 0};
+            if ((e = (hipError_t)rtk_check_read(c, 1)) != hipSuccess)
+                rc = hip_fail(e, "check counters");
+            else if (c[0])
+                rc = set_error(RT_EPANIC, "check build: " + std::to_string(c[0]) +
+                                              " decoded ref(s) past their array (first: kind " +
+                                              std::to_string(rtk::ref_kind((uint32_t)c[1])) + ", index " +
+                                              std::to_string(rtk::ref_index((uint32_t)c[1])) + ")");
+        }
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t bg, uint32_t flags, rt_world_info* out) {
     if (!s || !out) return set_error(RT_EINVAL, "null argument");
     if (world < 0 || (size_t)world >= s->objs.size() || s->objs[world].hidden)

@@ -20,7 +20,12 @@ import os
 
 import numpy as np
 
-from .capi import Api, RtCamera, RtError, RtRenderOpts, RtStats, d3, d4
+from .capi import Api, RtCamera, RtError, RtHitRecord, RtRay, RtRenderOpts, RtStats, d3, d4
+
+# rt_hit_record as a numpy record (80 B, the C layout)
+HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
+                      ("mat", "<i4"), ("flags", "<u4")])
+assert HIT_DTYPE.itemsize == C.sizeof(RtHitRecord)
 
 
 class Texture:
@@ -190,6 +195,29 @@ class Scene:
         cannot be opened: here that raises RtError(RT_EINVAL)."""
         rc = self.api.wavefront_load(self.s, os.fsencode(obj_path), 1 if vanilla_material else 0)
         return Hittables(self, self._c(rc), "list")
+
+
+    # ---- Hittable::hit (hit.rs:46-60)
+    def hit(self, world, rays, seed=0, flags=0):
+        """world.hit(Ray{origin, dir, time}, [1e-8, t_max]) for each row
+        (ox, oy, oz, dx, dy, dz, time, t_max) of the (n, 8) float64 array
+        `rays` (rt_world_hit).  Returns n records as a numpy structured array
+        (HIT_DTYPE: t, p, normal, u, v, mat, flags)."""
+        a = np.ascontiguousarray(rays, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) array: origin, direction, time, t_max")
+        n = a.shape[0]
+        out = np.zeros(n, dtype=HIT_DTYPE)
+        self._c(self.api.world_hit(self.s, world.h, int(seed), int(flags), a.ctypes.data_as(C.POINTER(RtRay)), n,
+                                   out.ctypes.data_as(C.POINTER(RtHitRecord))))
+        return out
+
+    def hit_device(self, world, rays_ptr, n, out_ptr, seed=0, flags=0, stream=None):
+        """rt_world_hit_device: n rt_ray at the device address rays_ptr, n
+        rt_hit_record written at out_ptr, enqueued on `stream` (a hipStream_t
+        as an integer; None = the default stream) without waiting."""
+        self._c(self.api.world_hit_device(self.s, world.h, int(seed), int(flags), C.c_void_p(int(rays_ptr)), int(n),
+                                          C.c_void_p(int(out_ptr)), C.c_void_p(stream) if stream else None))
 
 
 class Camera:
