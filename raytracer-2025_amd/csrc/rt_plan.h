@@ -1,7 +1,7 @@
 // rt_plan.h -- the host-side frame plan of a launch: which kernel tier a
 // flattened world takes, how a shard's stratum rows split into queue entries
 // (whole rows, tail parts, fine parts).  Pure host arithmetic, shared by the
-// product (the extern "C" rtk_* entry points in rt_kernel.hip, which
+// product (the extern "C" rtk_* entry points in rt_kernel_common.hip, which
 // rt_render.cpp calls) and the launcher's CPU test build
 // (tests/cpp/hip_stub.cpp: the same plan under TSan, against a stub device
 // layer).  No HIP calls here.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static ISA attribution of the basic tier's path kernel (C2) by phase.
 
-Compiles csrc/rt_kernel.hip for tier 0 as the product does (gfx950, -O3, no
+Compiles csrc/rt_kernel_path.hip for tier 0 as the product does (gfx950, -O3, no
 contraction, machine LICM off) with -DRT_ISA_MARKS -- an assembler comment at
 each phase boundary of the loop (RT_ISA_MARK: fields, walk / walk_visit /
 walk_sphere / walk_tail, park, miss, refill, draws, shade, camera) -- and
@@ -21,9 +21,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "raytracer-2025_amd", "csrc", "rt_kernel.hip")
+SRC = os.path.join(ROOT, "raytracer-2025_amd", "csrc", "rt_kernel_path.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
-         "-mllvm", "-disable-machine-licm", "-DRT_TIER_ONLY=0", "--offload-device-only", "-S"]
+         "-mllvm", "-disable-machine-licm", "-DRT_TIER=0", "--offload-device-only", "-S"]
 KERNEL = "_ZN3rtk14rt_path_kernelILi0ELb0EEEvPKNS_7KParamsE"
 
 

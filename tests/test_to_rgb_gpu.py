@@ -1,4 +1,4 @@
-"""The device output stage (srgb_u8 of rt_kernel.hip through rt_to_rgb_device:
+"""The device output stage (srgb_u8 of rt_kernel_common.hip through rt_to_rgb_device:
 ACES or not, sRGB OETF with ocml's pow, round, clamp) against the exact
 rational reference of tests/srgb_exact.py, on the inputs where it can go
 wrong: the +-64-ulp neighbourhood of every byte threshold, the +-4-ulp
