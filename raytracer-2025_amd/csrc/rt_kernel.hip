@@ -36,6 +36,7 @@
 #include "rt_sort4.h"
 #include "rt_sphere_filter.h"
 #include "rt_plan.h"
+#include "rt_queue.h"
 
 namespace rtk {
 
@@ -211,13 +212,6 @@ __device__ __forceinline__ void check_run(const SceneView& S, uint32_t first, ui
     if (n && first + n > S.n_ref[K_QUAD]) check_fail(make_ref(K_QUAD, first + n - 1));
 #endif
 }
-
-// n / d for n < 2^32, d < 2^20, from inv = 1/d rounded up: n * inv is at least
-// the quotient's integer part when d divides n (a representable product,
-// rounded to nearest, cannot fall below it) and below the next integer
-// otherwise (the excess n * 2^-52 / d stays under 1/d): three f64 / convert
-// instructions instead of a ~25-instruction integer division expansion.
-__device__ __forceinline__ uint32_t udiv_inv(uint32_t n, double inv) { return (uint32_t)((double)n * inv); }
 
 // ------------------------------------------------------------------ textures
 // texture.rs: SolidColor 33-36, CheckerTexture 60-73, ImageTexture 165-174,
@@ -2277,55 +2271,9 @@ __device__ __forceinline__ bool shade_hit_basic(const SceneView& S, Ray& ray, D3
 #ifndef RT_SHADE_BATCH_FLAT
 #define RT_SHADE_BATCH_FLAT 64
 #endif
-#ifndef RT_QUEUE_CHUNK
-// most entries a wave takes per queue atomic, with chunks shrinking as
-// left / (waves x RT_QUEUE_GUIDE): 512 / 16 against 256 / 8 -- half the
-// counter's atomics early, smaller pools late -- C2 186.3 -> 185.0 ms frame
-// and 1/8 shard 24.8 -> 24.4, C4 188.6 -> 186.2 and 29.8 -> 26.7, C3 +-0.5 %
-// (A/B, 2 interleaved reps each; 512 at guide 8: C2 frame -1.1 % but shard
-// +11 %; 512 / 32 and 1024 / 32: C2 shard +4-5 %)
-#define RT_QUEUE_CHUNK 512
-#endif
-#ifndef RT_QUEUE_CHUNK_MESH
-// the mesh tier's cap, a knob: its rounds are long (a dependent global load
-// per walk step) and a large pool can outlive the queue by milliseconds, but
-// smaller caps cost the whole frame in counter contention (at guide 8, cap
-// 128: C4 frame +2 %, 1/8 shard 30.0 -> 27.3 ms; 64: +6 %, 27.2 ms)
-#define RT_QUEUE_CHUNK_MESH RT_QUEUE_CHUNK
-#endif
-#ifndef RT_QUEUE_GUIDE
-#define RT_QUEUE_GUIDE 16  // guided chunks: left / (waves * GUIDE), 0 = fixed RT_QUEUE_CHUNK
-#endif
 #ifndef RT_MESH_WAVES
 #define RT_MESH_WAVES 4  // beats 2 waves (164.7 vs 263.8 ms, C4 64 spp) and 3 / 5 waves (+16 % / +12 %)
 #endif
-
-// Queue entry q -> its stratum-row item and samples [s_j, s_end) (Frame:
-// whole rows, then parts, then the fine parts of the frame's last rows).
-__device__ __forceinline__ void queue_entry(const Frame& F, uint32_t q, uint32_t& item, uint32_t& s_j,
-                                            uint32_t& s_end) {
-    const bool whole = q < F.whole_items, fine = q >= F.fine_q0;
-    const uint32_t qt = whole ? 0u : q - (fine ? F.fine_q0 : F.whole_items);  // (udiv_inv wants n < 2^32 in range)
-    const uint32_t np = fine ? F.parts2 : F.parts, pl = fine ? F.part_len2 : F.part_len;
-    const uint32_t it = udiv_inv(qt, fine ? F.inv_parts2 : F.inv_parts), part = qt - it * np;
-    item = whole ? q : (fine ? F.fine_item0 : F.whole_items) + it;
-    s_j = whole ? 0u : part * pl;
-    s_end = whole ? F.S : min(F.S, s_j + pl);
-}
-// The guided chunk of a wave whose pool ends at pool_end: about 1/GUIDE of
-// the samples left (as last seen) per wave of the grid, in the entries of
-// the region the next pool starts in; never below what the wave's lanes need
-// now (n lanes, avail entries in the pool), nor below Frame::chunk_min.
-__device__ __forceinline__ uint32_t guided_chunk(const Frame& F, uint32_t pool_end, uint32_t avail, uint32_t n) {
-    const uint32_t whole_left = F.whole_items > pool_end ? F.whole_items - pool_end : 0u;
-    const uint32_t p0 = max(pool_end, F.whole_items), part_left = F.fine_q0 > p0 ? F.fine_q0 - p0 : 0u;
-    const uint32_t f0 = max(pool_end, F.fine_q0), fine_left = F.queue_total > f0 ? F.queue_total - f0 : 0u;
-    const float g = ((float)whole_left * F.S_f + (float)part_left * F.part_len_f + (float)fine_left * F.part_len2_f) *
-                    F.inv_guide;
-    const float inv_per = whole_left ? F.inv_S_f : (part_left ? F.inv_part_len_f : F.inv_part_len2_f);
-    const uint32_t chunk = min((uint32_t)(g * inv_per), F.chunk_cap);
-    return max(max(chunk, whole_left ? F.chunk_min_whole : F.chunk_min), avail < n ? n - avail : 0u);
-}
 
 // Launch parameters live in device memory and are read where they are used
 // (scalar loads), not pinned in SGPRs for the life of the kernel.
@@ -2487,16 +2435,9 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     uint32_t vertex = 0;
     uint32_t n_rays = 0, n_panics = 0;
 
-    // wave-uniform: the queue entries this wave holds.  Wave w starts with the
-    // 64 entries [64 w, 64 w + 64) -- no atomic at launch: 4096 waves taking
-    // their first chunk from one counter at once waited up to 2.9 ms for it
-    // (scripts/lone_wave.py) -- and the counter hands out entries from
-    // Frame::static_entries on.  `dry`: an atomic of this wave has passed the
-    // end of the queue, so none will hand out entries any more -- lanes that
-    // need one leave without another atomic (the drain's waves waited ~70 us
-    // a round on the counter the whole grid hammered).
-    uint32_t pool_next = (blockIdx.x * (BLK / 64) + threadIdx.x / 64) * 64u, pool_end = pool_next + 64u;
-    bool dry = false;
+    // wave-uniform, in scalar registers: the queue entries this wave holds
+    // (rt_queue.h)
+    QueuePool pool = pool_of_wave(blockIdx.x * (BLK / 64) + threadIdx.x / 64);
     Diag dg;
     Trav<TIER> T;
     bool walking = false;
@@ -2514,61 +2455,39 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     unsigned long long trace_tq = trace_t0;
 #endif
     // ---- refill: the lanes that need a queue entry take one (false: the
-    // queue is done and this lane leaves the loop)
+    // queue is done and this lane leaves the loop).  Both loops below run it,
+    // in uniform control flow: the pool is the wave's.
     auto refill = [&]() -> bool {
-        // wave-aggregated dequeue of stratum rows.  The wave takes
-        // RT_QUEUE_CHUNK items per atomic into a wave-uniform pool and hands them
-        // to its lanes in rank order: one contended atomic per chunk, not one per
-        // main-loop iteration (every iteration some lane of the wave needs work).
+        // wave-aggregated dequeue of stratum rows.  The wave takes a chunk of
+        // entries per atomic into its pool and hands them to its lanes in
+        // rank order: one contended atomic per chunk, not one per main-loop
+        // iteration (every iteration some lane of the wave needs work).
         const unsigned long long mask = __ballot(need);
         if (mask) {
-            const uint32_t n = (uint32_t)__popcll(mask);
-            const uint32_t avail = pool_end - pool_next;
-            uint32_t fresh = 0;
-            // guided chunk: about 1/GUIDE of the items left (as last seen) per
-            // wave of the grid, so the last chunks are small and waves finish
-            // together; never below what the wave's lanes need now, nor below
-            // Frame::chunk_min.  Near the end a wave takes only what its lanes
-            // need: a pool held by a slow wave (deep glass paths) is work the
-            // idle waves cannot take (scripts/lane_trace.py).
-            // (the chunk in the entries it takes: a pool of whole rows taken
-            // as the tail starts is no larger in samples than the tail's
-            // pools -- it would outlast them)
-            const uint32_t chunk = RT_QUEUE_GUIDE ? guided_chunk(F, pool_end, avail, n) : (uint32_t)RT_QUEUE_CHUNK;
             // the lane's rank among the needy lanes (the leader: rank 0 with
             // need); the leader's atomic result is read with v_readlane -- no
             // lane id held across the loop, no ds_bpermute
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-            if (avail < n) {
-                if (!dry) {
-                    const uint32_t leader = __ffsll((long long)mask) - 1;
+            const QueuePass pass = pool_take(pool, F, (uint32_t)__popcll(mask), [&](uint32_t chunk) -> uint32_t {
+                const uint32_t leader = __ffsll((long long)mask) - 1;
 #ifdef RT_WAVE_TRACE
-                    const unsigned long long ta = __builtin_amdgcn_s_memrealtime();
+                const unsigned long long ta = __builtin_amdgcn_s_memrealtime();
 #endif
-                    if (need && rank == 0) fresh = atomicAdd(queue, chunk);
-                    fresh = __builtin_amdgcn_readlane(fresh, leader) + F.static_entries;
+                uint32_t fresh = 0;
+                if (need && rank == 0) fresh = atomicAdd(queue, chunk);
+                fresh = __builtin_amdgcn_readlane(fresh, leader);
 #ifdef RT_WAVE_TRACE
-                    {
-                        const unsigned long long tb = __builtin_amdgcn_s_memrealtime();
-                        trace_atomic_ticks += tb - ta;
-                        if (trace_atomics++ == 0) trace_atomic_first = tb - trace_t0;
-                    }
-#endif
-                    dry = fresh + chunk >= F.queue_total;
-                } else {
-                    fresh = F.queue_total;  // past the end: the needy lanes leave
+                {
+                    const unsigned long long tb = __builtin_amdgcn_s_memrealtime();
+                    trace_atomic_ticks += tb - ta;
+                    if (trace_atomics++ == 0) trace_atomic_first = tb - trace_t0;
                 }
-            }
-            const uint32_t old_next = pool_next;
-            if (avail < n) {
-                pool_next = fresh + (n - avail);
-                pool_end = fresh + chunk;
-            } else {
-                pool_next += n;
-            }
+#endif
+                return fresh;
+            });
             if (need) {
-                const uint32_t q = rank < avail ? old_next + rank : fresh + (rank - avail);
+                const uint32_t q = pool_entry(pass, rank);
                 if (q >= F.queue_total) return false;
                 need = false;
 #ifdef RT_WAVE_TRACE
@@ -2579,11 +2498,20 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                 trace_tq = __builtin_amdgcn_s_memrealtime();
 #endif
                 uint32_t item, s_end;
-                queue_entry(F, q, item, s_j, s_end);
-                acc = d3(0, 0, 0);
+                if constexpr (B4)
+                    queue_entry(F, q, pass.q_lo, pass.q_end, item, s_j, s_end);
+                else
+                    queue_entry(F, q, 0u, ~0u, item, s_j, s_end);
+                if constexpr (ACC_LDS)  // the entry's sum lives in LDS (flat tier)
+                    pst[6 * RT_BLOCK] = 0.0, pst[7 * RT_BLOCK] = 0.0, pst[8 * RT_BLOCK] = 0.0;
+                else
+                    acc = d3(0, 0, 0);
                 const uint32_t pl = udiv_inv(item, F.inv_S), s_i = item - pl * F.S;
                 sie = s_i | (s_end << 16);
-                slot = q;
+                if constexpr (ACC_LDS)
+                    pit[BLK].y = q;
+                else
+                    slot = q;
                 const uint32_t prow = udiv_inv(pl, F.inv_W);
                 rng.pixel = (F.row_offset + prow * F.row_stride) * F.W + (pl - prow * F.W);
             }
@@ -2713,8 +2641,8 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
             RT_DIAG_ONLY(const unsigned long long t_b1 = __builtin_amdgcn_s_memtime(); dg.cyc_trace += t_b1 - t_b0;)
             // a walk that carries over this shading round is parked;
             // the lane skips the rest of the iteration but for the refill,
-            // which every lane of the wave runs: the queue pool (pool_next,
-            // pool_end, dry) is wave-uniform state and must be updated in
+            // which every lane of the wave runs: the queue pool (QueuePool:
+            // next, end, dry) is wave-uniform state and must be updated in
             // uniform control flow, or a parked lane would keep a stale copy
             RT_ISA_MARK("park");
             const bool carry = BATCH < 64 && walking;
@@ -2779,84 +2707,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     } else {
     for (;;) {
         RT_DIAG_ONLY(const unsigned long long t_loop0 = __builtin_amdgcn_s_memtime(); ++dg.main_iters;)
-        // ---- refill: wave-aggregated dequeue of stratum rows.  The wave takes
-        // RT_QUEUE_CHUNK items per atomic into a wave-uniform pool and hands them
-        // to its lanes in rank order: one contended atomic per chunk, not one per
-        // main-loop iteration (every iteration some lane of the wave needs work).
-        const unsigned long long mask = __ballot(need);
-        if (mask) {
-            const uint32_t n = (uint32_t)__popcll(mask);
-            const uint32_t avail = pool_end - pool_next;
-            uint32_t fresh = 0;
-            // guided chunk: about 1/GUIDE of the items left (as last seen) per
-            // wave of the grid, so the last chunks are small and waves finish
-            // together; never below what the wave's lanes need now, nor below
-            // Frame::chunk_min.  Near the end a wave takes only what its lanes
-            // need: a pool held by a slow wave (deep glass paths) is work the
-            // idle waves cannot take (scripts/lane_trace.py).
-            // (the chunk in the entries it takes: a pool of whole rows taken
-            // as the tail starts is no larger in samples than the tail's
-            // pools -- it would outlast them)
-            const uint32_t chunk = RT_QUEUE_GUIDE ? guided_chunk(F, pool_end, avail, n) : (uint32_t)RT_QUEUE_CHUNK;
-            // the lane's rank among the needy lanes (the leader: rank 0 with
-            // need); the leader's atomic result is read with v_readlane -- no
-            // lane id held across the loop, no ds_bpermute
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-            if (avail < n) {
-                if (!dry) {
-                    const uint32_t leader = __ffsll((long long)mask) - 1;
-#ifdef RT_WAVE_TRACE
-                    const unsigned long long ta = __builtin_amdgcn_s_memrealtime();
-#endif
-                    if (need && rank == 0) fresh = atomicAdd(queue, chunk);
-                    fresh = __builtin_amdgcn_readlane(fresh, leader) + F.static_entries;
-#ifdef RT_WAVE_TRACE
-                    {
-                        const unsigned long long tb = __builtin_amdgcn_s_memrealtime();
-                        trace_atomic_ticks += tb - ta;
-                        if (trace_atomics++ == 0) trace_atomic_first = tb - trace_t0;
-                    }
-#endif
-                    dry = fresh + chunk >= F.queue_total;
-                } else {
-                    fresh = F.queue_total;  // past the end: the needy lanes leave
-                }
-            }
-            const uint32_t old_next = pool_next;
-            if (avail < n) {
-                pool_next = fresh + (n - avail);
-                pool_end = fresh + chunk;
-            } else {
-                pool_next += n;
-            }
-            if (need) {
-                const uint32_t q = rank < avail ? old_next + rank : fresh + (rank - avail);
-                if (q >= F.queue_total) break;
-                need = false;
-#ifdef RT_WAVE_TRACE
-                ++trace_items;
-                trace_q = q;
-                trace_rays = n_rays;
-                trace_steps_q = trace_steps;
-                trace_tq = __builtin_amdgcn_s_memrealtime();
-#endif
-                uint32_t item, s_end;
-                queue_entry(F, q, item, s_j, s_end);
-                if constexpr (ACC_LDS)  // the entry's sum lives in LDS (flat tier)
-                    pst[6 * RT_BLOCK] = 0.0, pst[7 * RT_BLOCK] = 0.0, pst[8 * RT_BLOCK] = 0.0;
-                else
-                    acc = d3(0, 0, 0);
-                const uint32_t pl = udiv_inv(item, F.inv_S), s_i = item - pl * F.S;
-                sie = s_i | (s_end << 16);
-                if constexpr (ACC_LDS)
-                    pit[BLK].y = q;
-                else
-                    slot = q;
-                const uint32_t prow = udiv_inv(pl, F.inv_W);
-                rng.pixel = (F.row_offset + prow * F.row_stride) * F.W + (pl - prow * F.W);
-            }
-        }
+        if (!refill()) break;
         if (!in_path) {
             // ---- Camera::get_ray (camera.rs:247-273), vertex 0
             const uint32_t s_i = sie & 0xFFFFu, py = udiv_inv(rng.pixel, F.inv_W), px = rng.pixel - py * F.W;
