@@ -1,5 +1,6 @@
 // rt_kernel.h -- interface between the host render driver (rt_render.cpp) and
-// the gfx950 kernels (rt_kernel.hip).
+// the gfx950 kernels (rt_kernel_path.hip, rt_kernel_hit.hip,
+// rt_kernel_common.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,6 +70,10 @@ __host__ __device__ constexpr bool tier_full_bvh(int t) { return t == TIER_FULL 
 __host__ __device__ constexpr uint32_t lds_stack_entries(int t) {
     return t == TIER_BASIC ? RT_STACK_BASIC : t == TIER_MESH ? RT_STACK_MESH : tier_full_bvh(t) ? RT_STACK_FULL : RT_STACK_FLAT;
 }
+// basic tier: the nodes its LDS copy holds, whole (the wide variant) and
+// beside the park area; the launcher picks the variant by the second
+constexpr uint32_t NODE_LDS_CAP = RT_NODE_LDS_BYTES / sizeof(DNode4);
+constexpr uint32_t NODE_LDS_CAP_BATCH = RT_NODE_LDS_BATCH_BYTES / sizeof(DNode4);
 }  // namespace rtk
 
 // Camera::initilize results (camera.rs:204-245) for one shard.

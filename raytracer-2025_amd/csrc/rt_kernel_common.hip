@@ -2,7 +2,16 @@
 // and the hit queries: the output stage (reduce, to_rgb, deinterleave), the
 // math and walk self-tests, the frame plan's entry points and the frame
 // launcher, which calls the tiers through rt_path_entry.h.
-#include "rt_kernel.hip"
+#include <hip/hip_runtime.h>
+
+#include "../../include/rt_mi355x.h"
+#include "rt_kernel.h"
+#include "rt_math.h"
+#include "rt_slab.h"
+#include "rt_sphere_filter.h"
+#include "rt_plan.h"
+#include "rt_queue.h"
+#include "rt_frame.h"
 #include "rt_path_entry.h"
 
 namespace rtk {

@@ -1,7 +1,17 @@
 // rt_kernel_hit.hip -- rt_world_hit's kernels (rt_hit_kernel) and their host
 // entry point.  An object of its own in the product build, so that no
 // path-kernel object sees a second caller of the walk or of make_record.
-#include "rt_kernel.hip"
+#include <hip/hip_runtime.h>
+
+#include "../../include/rt_mi355x.h"
+#include "rt_kernel.h"
+#include "rt_math.h"
+#include "rt_builds.h"
+#include "rt_geom.h"
+#include "rt_stack.h"
+#include "rt_walk.h"
+#include "rt_walk4.h"
+#include "rt_record.h"
 
 namespace rtk {
 

@@ -5,7 +5,7 @@
 // Transform::hit shapes.rs:88, ConstantMedium::hit volume.rs:37).  Here it is
 // one read-only blob of typed arrays, and every edge of the tree is a 32-bit
 // `ref` = kind (top 4 bits) | index (low 28 bits), walked by an explicit
-// per-lane stack (rt_kernel.hip).
+// per-lane stack (rt_stack.h).
 //
 // Layout choices (DESIGN.md "Data layout in HBM"):
 //  - a BVH node is one record holding what is needed to test every child
@@ -145,7 +145,7 @@ struct alignas(16) DMedium {
     uint32_t medium_id;
     // > 0: the boundary is planar_n quads / triangles stored consecutively at
     // planars[planar_first ..] (build_box's six quads), inside at most two
-    // Transforms, tested in one pass (rt_kernel.hip medium_hit); 0: any other
+    // Transforms, tested in one pass (rt_walk.h medium_hit); 0: any other
     // boundary, walked twice
     uint32_t planar_n;
     uint32_t planar_first;

@@ -3,7 +3,7 @@
 // it and takes the next chunk from the frame's counter (pool_take), the
 // chunk's size (guided_chunk) and the decode of an entry into its stratum row
 // and samples (queue_entry).  Plain integer and f32 arithmetic, templates over
-// the frame type (rt_kernel.hip Frame: the fields named here), so that the
+// the frame type (rt_frame.h Frame: the fields named here), so that the
 // same text compiles for the host: tests/cpp/pool_prop.cpp drives simulated
 // waves through it.  How a frame splits into entries is rt_plan.h's business.
 //

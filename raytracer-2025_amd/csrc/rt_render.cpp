@@ -283,7 +283,7 @@ void destroy_render_state(RenderState* r) {
 // the full tier, whose walk has no fallback: -1 with RT_ESTACK set).
 static int prepare_tier(HostWorld& hw) {
     int tier = rtk_tier_for(hw.features);
-    // the basic tier's walk words hold 15-bit sphere indices (rt_kernel.hip bword)
+    // the basic tier's walk words hold 15-bit sphere indices (rt_stack.h bword)
     if (tier == rtk::TIER_BASIC && hw.spheres.size() > 32768) tier = rtk::TIER_MESH;
     // and its 4-B stack entries hold 15-bit node / list indices
     if (tier == rtk::TIER_BASIC && hw.list_children.size() >= 32768) tier = rtk::TIER_MESH;
@@ -345,7 +345,7 @@ static void pack_world(const HostWorld& hw, std::vector<char>& blob, rtk::SceneV
     v.textures = (const rtk::DTexture*)off(put(blob, hw.textures));
     v.texels = (const float*)off(put(blob, hw.texels));
     v.perlin = (const rtk::DPerlin*)off(put(blob, hw.perlin));
-    // the mesh tier reads 128 B from any record's address (rt_kernel.hip
+    // the mesh tier reads 128 B from any record's address (rt_walk.h
     // unified_load): slack past the last array
     blob.resize(((blob.size() + 255) & ~(size_t)255) + 256, 0);
 }
@@ -989,7 +989,7 @@ static int32_t launch(rt_scene* s, int32_t world, int32_t lights, const rt_camer
 }
 
 // check build only (make check): the kernel's count of decoded refs past
-// their arrays on the current device (rt_kernel.hip ref_idx); absent from
+// their arrays on the current device (rt_builds.h ref_idx); absent from
 // the product library
 extern "C" __attribute__((weak)) int rtk_check_read(unsigned long long* out, int reset);
 

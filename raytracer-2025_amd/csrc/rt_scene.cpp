@@ -238,7 +238,7 @@ double half_area(const Box3& b) {
     return dx * dy + dy * dz + dz * dx;
 }
 
-constexpr int MAX_XF_NESTING = 2;  // rt_kernel.hip MAX_XF
+constexpr int MAX_XF_NESTING = 2;  // rt_geom.h XfIds
 
 struct Flattener {
     const rt_scene* s;
@@ -594,7 +594,7 @@ struct Flattener {
     }
 
     // Returns (ref, need): need = traversal-stack entries used below the entry
-    // that held this ref (rt_kernel.hip trace()).
+    // that held this ref (rt_walk.h trace_step).
     std::pair<uint32_t, uint32_t> emit(int id, bool in_boundary, int xf_depth) {
         auto it = memo.find(id);
         if (it != memo.end()) return it->second;
@@ -793,7 +793,7 @@ struct Flattener {
 // or an RT_E* code: a BVH or a ConstantMedium has no pdf_value / random
 // (hit.rs:52-60 unimplemented!(): the reference panics at the first light
 // sample), an empty list panics in Hittables::random (hits.rs:71-73).
-constexpr int LIGHT_TREE_DEPTH = 4;  // rt_kernel.hip RT_LIGHT_DEPTH
+constexpr int LIGHT_TREE_DEPTH = 4;  // rt_lights.h RT_LIGHT_DEPTH
 int light_tree(const rt_scene* s, int id, int depth, std::string& err) {
     const Obj& o = s->objs[id];
     switch (o.kind) {
@@ -974,7 +974,7 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
     }
     // Wrapper materials (DiffuseLight with a material, Mix): the C3 / C5 tiers
     // take one level whose Mix ratio is a constant; deeper trees and
-    // Mix::from_image ratios run the FULL_GL tier (rt_kernel.hip emitted_tree),
+    // Mix::from_image ratios run the FULL_GL tier (rt_shade.h emitted_tree),
     // up to RT_MAT_DEPTH (4) wrapper levels.
     std::function<int(int)> wrap_depth = [&](int mid) -> int {
         const rtk::DMaterial& m = out.materials[mid];
@@ -1589,7 +1589,7 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
 #if RT_BVH4_SPHERES_FIRST
         // basic tier: sphere children in the low slots, boxes after them, empty
         // slots last -- a wave runs a slot's slab test only when one of its
-        // lanes has a child there (rt_kernel.hip visit4_rows); most leaf-level
+        // lanes has a child there (rt_walk4.h visit4_rows); most leaf-level
         // nodes hold 2 or 3 spheres
         if (filter_spheres)
             std::stable_partition(ch.begin(), ch.end(),

@@ -1,10 +1,10 @@
 // rt_slab.h -- the conservative f32 box test every kernel tier walks with.
 //
-// Host and device: the kernel (rt_kernel.hip) runs it, and the CPU property
-// test (tests/test_slab_cpu.py, tests/cpp/slab_prop.cpp) checks it against the
-// slab test of aabb.rs:62-78 evaluated in extended precision.  The basic
-// tier walks with the sign-ordered form of the same test (RaySF, slab_sorted_f
-// at the end of this file; tests/test_slab_sorted_cpu.py).
+// Host and device: the kernels' walk (rt_walk.h, rt_walk4.h) runs it, and the
+// CPU property test (tests/test_slab_cpu.py, tests/cpp/slab_prop.cpp) checks
+// it against the slab test of aabb.rs:62-78 evaluated in extended precision.
+// The basic tier walks with the sign-ordered form of the same test (RaySF,
+// slab_sorted_f at the end of this file; tests/test_slab_sorted_cpu.py).
 //
 // aabb.rs:62-78: per axis t0 = (lo - o) / d, t1 = (hi - o) / d, the interval
 // [min, max] of the two intersected with the ray's [t_min, t_max]; a hit when
@@ -160,6 +160,26 @@ RT_HD float f32_down(double x) {
     }
     return f;
 }
+
+// Closest-hit state of one traversal: t and its f32 upper bound.
+struct Closest {
+    double c;
+    float c_f;
+    // c_f = (float)t plus at least one ulp: an upper bound of t in two
+    // instructions (|f| * 2^-23 >= 1 ulp of f, and (float)t is within half an
+    // ulp), where the exact round-up takes a compare-and-step sequence.
+    RT_HD void set(double t) {
+        c = t;
+        const float f = (float)t;
+        c_f = fmaf(fabsf(f), 1.1920928955078125e-07f, f);
+    }
+    // a hit t <= c that never loosens c_f (basic tier's sphere rounds)
+    RT_HD void lower(double t) {
+        c = t;
+        const float f = (float)t;
+        c_f = fminf(c_f, fmaf(fabsf(f), 1.1920928955078125e-07f, f));
+    }
+};
 
 // The f32 box of a basic-tier sphere child {cx, cy, cz, r} (rth::bvh4_convert):
 // the walk slab-tests it and runs the exact f64 Sphere::hit (sphere.rs:77-108)

@@ -1,12 +1,12 @@
 // rt_sort4.h -- the basic tier's 4-wide node visit sorts its hit box children
 // as packed 32-bit words.
 //
-// Host and device: the kernel (rt_kernel.hip visit4_rows) runs it, and the CPU
+// Host and device: the kernel (rt_walk4.h visit4_rows) runs it, and the CPU
 // property test (tests/test_sort4_cpu.py, tests/cpp/sort4_prop.cpp) checks the
 // same text.
 //
 // A slot's sort word is the upper 16 bits of its f32 entry distance above the
-// child's 16-bit ref code (the upper half of its walk word, rt_kernel.hip
+// child's 16-bit ref code (the upper half of its walk word, rt_stack.h
 // bword):
 //     sort word  = (bits(entry) & 0xffff0000) | (walk word >> 16)
 //  - The entry distance of a hit slot is slab_f's (rt_slab.h): the maximum of

@@ -2,7 +2,7 @@
 //
 // The path kernels no longer call it: since round 7 a sphere child of a basic-
 // tier node carries its own f32 box and is slab-tested like any other child
-// (rt_slab.h sphere_box_f, rt_kernel.hip visit4_rows), which costs fewer VALU
+// (rt_slab.h sphere_box_f, rt_walk4.h visit4_rows), which costs fewer VALU
 // instructions a visit than this filter did.  The functions stay, host and
 // device, with their tests: the CPU property test (tests/test_filter_cpu.py,
 // tests/cpp/filter_prop.cpp) checks them against the exact f64 Sphere::hit

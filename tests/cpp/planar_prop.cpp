@@ -38,7 +38,7 @@ static Prim make(V Q, V u, V v) {
     return p;
 }
 
-// the kernel's planar_t (rt_kernel.hip), f64
+// the kernel's planar_t (rt_geom.h), f64
 static bool exact(const Prim& P, bool tri, V o, V d, double tmin, double tmax, double& t) {
     const double denom = dot(P.n, d);
     if (std::fabs(denom) < 1e-8) return false;

@@ -28,7 +28,7 @@
 
 using namespace rtk;
 
-// the queue's fields of rt_kernel.hip Frame, filled as fill_kparams fills them
+// the queue's fields of rt_frame.h Frame, filled as fill_kparams fills them
 struct QFrame {
     uint32_t W, rows, S, total_items;
     uint32_t parts, part_len, queue_total, whole_items;

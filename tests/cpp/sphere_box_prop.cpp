@@ -42,11 +42,6 @@ static float round_up_f(double x) {
     if ((double)f < x) f = std::nextafter(f, INFINITY);
     return f;
 }
-// as rt_kernel.hip's Closest::set
-static float closest_cf(double t) {
-    const float f = (float)t;
-    return fmaf(fabsf(f), 1.1920928955078125e-07f, f);
-}
 
 int main(int argc, char** argv) {
     const long n = argc > 1 ? std::atol(argv[1]) : 1000000;
@@ -143,7 +138,9 @@ int main(int argc, char** argv) {
         if (bk == 1) cb = std::exp(std::log(1e-6) + U(rng) * std::log(1e10));
         else if (bk == 2 && t_any >= 0) cb = t_any;
         else if (bk == 3 && t_any >= 0) cb = t_any * (1.0 + U(rng) * 1e-5);
-        const float cf = std::isinf(cb) ? INFINITY : closest_cf(cb);
+        rtk::Closest cl;  // the walk's own bound (rt_slab.h Closest::set)
+        cl.set(cb);
+        const float cf = std::isinf(cb) ? INFINITY : cl.c_f;
         const double tx = exact_sphere_t(c, r, o, d, 1e-8, cb);
 
         float lo[3], hi[3];

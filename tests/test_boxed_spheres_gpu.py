@@ -1,6 +1,6 @@
 """The basic tier's boxed sphere children against the oracle: a sphere child of
 a 4-wide node carries its own f32 box, the walk slab-tests it and queues the
-sphere for the exact f64 Sphere::hit on a box hit (rt_kernel.hip visit4_rows,
+sphere for the exact f64 Sphere::hit on a box hit (rt_walk4.h visit4_rows,
 rth::bvh4_convert).  A box admits more rays than the sphere does, so these
 small worlds load the per-lane queue and the boxes' edge cases; none of it may
 change a sample: the f32 frames are equal to the oracle's and no (pixel,

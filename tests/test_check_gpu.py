@@ -1,7 +1,7 @@
 """The check build (`make -C raytracer-2025_amd check`, librt_mi355x_check.so):
 every ref the kernel decodes -- walk steps, a node's sphere slots, planar
 runs, hit records, lights -- is checked against its array's size
-(rt_kernel.hip ref_idx, SceneView::n_ref), and a ref past its array makes the
+(rt_builds.h ref_idx, SceneView::n_ref), and a ref past its array makes the
 render fail with RT_EPANIC naming it instead of reading past the array.
 
 Round 3's bvh4_relayout named a record past the triangle array and changed 13

@@ -5,7 +5,7 @@ medium boundaries twice (volume.rs:44-48):
 * planar runs: a list step tests up to 8 consecutive quads / triangles at once
   (rt_scene.cpp DBoxF::run) -- runs of quads, of triangles, mixed, a list
   longer than one run, a run inside a Transform;
-* one-pass medium boundaries (rt_kernel.hip boundary_onepass): a box of quads
+* one-pass medium boundaries (rt_walk.h boundary_onepass): a box of quads
   inside one and two Transforms, a triangle boundary, a sphere boundary bare
   and inside a Transform, a camera inside a medium, and a 7-quad boundary that
   is longer than the one-pass limit (the two-walk path).

@@ -1,4 +1,4 @@
-"""The basic tier's miss under a sky gradient (rt_kernel.hip shade, miss
+"""The basic tier's miss under a sky gradient (rt_shade.h shade, miss
 branch) makes only the unit direction's y quotient.  Its panic flag must be
 the one unit() gives (rt_math.h: u = v / |v|, ok = every u_i finite), which
 the kernel states as: |v| not NaN, not 0, and every v_i finite.  This checks
@@ -18,7 +18,7 @@ def _ok_unit(v):  # unit() = divs(v, |v|) = (1 / |v|) * v (rt_math.h, vec3.rs:22
     return np.isfinite(u).all(axis=1), u[:, 1]
 
 
-def _ok_sky(v):  # the kernel's statement (rt_kernel.hip shade, basic tier's sky miss)
+def _ok_sky(v):  # the kernel's statement (rt_shade.h shade, basic tier's sky miss)
     l = _len(v)
     return ~(np.isnan(l) | (l == 0.0) | ~np.isfinite(v).all(axis=1)), ((1.0 / l) * v[:, 1])
 

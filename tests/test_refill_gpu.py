@@ -1,5 +1,5 @@
 """The work queue's hand-out on the GPU against the oracle.  Every tier's loop
-of rt_path_kernel (raytracer-2025_amd/csrc/rt_kernel.hip) takes its queue
+of rt_path_kernel (raytracer-2025_amd/csrc/rt_kernel_path.hip) takes its queue
 entries through one refill (rt_queue.h): the wave's pool of entries lives in
 scalar registers, a chunk is sized only on the pass that takes one from the
 counter, and a pass that lies in one region of the queue (whole rows, parts,

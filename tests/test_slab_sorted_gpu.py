@@ -2,7 +2,7 @@
 lane reads each axis' near and far row of a node from the block's LDS copy at
 an address offset by the sign of its ray's 1/d, and the visit tests the slots
 with slab_sorted_f -- the six plane distances of slab_f without the per-axis
-min / max (raytracer-2025_amd/csrc/rt_slab.h, rt_kernel.hip load_node4_sorted
+min / max (raytracer-2025_amd/csrc/rt_slab.h, rt_walk4.h load_node4_sorted
 and visit4_rows; the test itself on CPU: tests/test_slab_sorted_cpu.py).  The
 walk must visit the same nodes in the same order, so no sample may change: the
 f32 frames are equal to the oracle's (RMSE 0), no (pixel, stratum row) sum

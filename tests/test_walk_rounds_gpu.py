@@ -1,6 +1,6 @@
 """The basic tier's walk loop and its sphere-round decision on the GPU against
 the oracle.  The batch loop of rt_path_kernel<0, false>
-(raytracer-2025_amd/csrc/rt_kernel.hip) calls trace4_step with every lane of
+(raytracer-2025_amd/csrc/rt_kernel_path.hip) calls trace4_step with every lane of
 the wave in uniform control flow: a lane whose walk is over, or that has no
 path, holds the empty state and must do nothing there; the step counts the
 lanes in the walk from the state itself (a word to walk or a sphere queued)
