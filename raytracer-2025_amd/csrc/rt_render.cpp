@@ -289,7 +289,7 @@ static int prepare_tier(HostWorld& hw) {
     if (tier == rtk::TIER_BASIC && hw.list_children.size() >= 32768) tier = rtk::TIER_MESH;
     // the basic tier's kernel reads every 4-wide node from its LDS copy
     if (tier == rtk::TIER_BASIC &&
-        bvh4_convert(hw, RT_STACK_BASIC, true, RT_NODE_LDS_BYTES / sizeof(rtk::DNode4)) > RT_STACK_BASIC)
+        bvh4_convert(hw, RT_STACK_BASIC, true, rtk::NODE_LDS_CAP, rtk::NODE_LDS_CAP_BATCH) > RT_STACK_BASIC)
         tier = rtk::TIER_MESH;
     if (tier == rtk::TIER_MESH && bvh4_convert(hw, RT_STACK_MAX, false) > RT_STACK_MAX) tier = rtk::TIER_FULL;
     if (tier == rtk::TIER_FULL && hw.nodes.empty()) return rtk::TIER_FULL_FLAT;

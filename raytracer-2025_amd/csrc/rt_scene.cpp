@@ -240,6 +240,13 @@ double half_area(const Box3& b) {
 
 constexpr int MAX_XF_NESTING = 2;  // rt_geom.h XfIds
 
+// The SAH rebuild splits a range of at most this many items by a full sweep
+// over the sorted centroids, a larger one by 32 bins an axis (0: bins only --
+// an A/B knob of the build)
+#ifndef RT_SAH_SWEEP_MAX
+#define RT_SAH_SWEEP_MAX 2048
+#endif
+
 struct Flattener {
     const rt_scene* s;
     HostWorld& out;
@@ -371,7 +378,8 @@ struct Flattener {
         uint32_t ref, need;
         bool local;
     };
-    // Binned SAH (32 bins x 3 axes) over items[b, e); leaves hold one object,
+    // SAH build over items[b, e) (sah_build: binned, 32 bins x 3 axes; a full
+    // sweep for small ranges); leaves hold one object,
     // the parent carries each child's box.  Returns (ref, need).  Nodes are
     // numbered in preorder (a node, its left subtree, its right subtree); the
     // two halves of a large node are built at once into their own buffers and
@@ -388,9 +396,61 @@ struct Flattener {
         }
         return {r.local ? r.ref + off : r.ref, r.need};
     }
-    Built sah_build(std::vector<Item>& it, size_t b, size_t e, NodeBuf& nb, int par) {
-        if (e - b == 1) return {it[b].ref, it[b].need, false};
-        size_t mid = b + (e - b) / 2;
+    // A split of items[b, e) and its cost area(L) |L| + area(R) |R| (infinite:
+    // no split separates the items).  Both halves keep the range's order.
+    struct Split {
+        double cost = std::numeric_limits<double>::infinity();
+        std::vector<uint8_t> left;  // sweep: per position of the range, 1 = goes left
+        int axis = -1, bin = 0;     // binned: centroid bins 0 .. bin of `axis` go left
+        double cmin = 0, ext = 0;
+    };
+    static constexpr int SAH_BINS = 32;
+    static int sah_bin(double c, double cmin, double ext) {
+        int bin = (int)((c - cmin) / ext * SAH_BINS);
+        return bin < 0 ? 0 : (bin >= SAH_BINS ? SAH_BINS - 1 : bin);
+    }
+    // Full-sweep SAH over items[b, e): on each axis the items in centroid order
+    // (ties by position in the range: a total order, the same on every run),
+    // every prefix against its suffix; the cheapest of all three axes, the
+    // first found among equals.  A boundary between two centroid bins is such a
+    // prefix, so this split never costs more than binned_split's.
+    static Split sweep_split(const std::vector<Item>& it, size_t b, size_t e) {
+        const size_t n = e - b;
+        Split best;
+        std::vector<std::pair<double, uint32_t>> ord(n), best_ord;
+        std::vector<double> right_area(n);
+        size_t best_cnt = 0;
+        for (int k = 0; k < 3; ++k) {
+            for (size_t i = 0; i < n; ++i) ord[i] = {it[b + i].c[k], (uint32_t)i};
+            std::sort(ord.begin(), ord.end());
+            if (!(ord[n - 1].first - ord[0].first > 0)) continue;  // no extent on this axis
+            Box3 acc = Box3::empty();
+            for (size_t i = n - 1; i > 0; --i) {
+                acc = acc.unite(it[b + ord[i].second].box);
+                right_area[i] = half_area(acc);
+            }
+            acc = Box3::empty();
+            bool found = false;
+            for (size_t i = 0; i + 1 < n; ++i) {
+                acc = acc.unite(it[b + ord[i].second].box);
+                const double cost = half_area(acc) * (double)(i + 1) + right_area[i + 1] * (double)(n - i - 1);
+                if (cost < best.cost) {
+                    best.cost = cost;
+                    best.axis = k;
+                    best_cnt = i + 1;
+                    found = true;
+                }
+            }
+            if (found) best_ord = ord;
+        }
+        if (best.axis >= 0) {
+            best.left.assign(n, 0);
+            for (size_t i = 0; i < best_cnt; ++i) best.left[best_ord[i].second] = 1;
+        }
+        return best;
+    }
+    // Binned SAH over items[b, e): 32 centroid bins an axis, the cheapest boundary.
+    static Split binned_split(const std::vector<Item>& it, size_t b, size_t e) {
         double cmin[3], cmax[3];
         for (int k = 0; k < 3; ++k) {
             cmin[k] = std::numeric_limits<double>::infinity();
@@ -401,9 +461,8 @@ struct Flattener {
                 cmin[k] = std::fmin(cmin[k], it[i].c[k]);
                 cmax[k] = std::fmax(cmax[k], it[i].c[k]);
             }
-        constexpr int NB = 32;
-        double best = std::numeric_limits<double>::infinity();
-        int best_axis = -1, best_bin = 0;
+        constexpr int NB = SAH_BINS;
+        Split best;
         for (int k = 0; k < 3; ++k) {
             double ext = cmax[k] - cmin[k];
             if (!(ext > 0)) continue;
@@ -411,8 +470,7 @@ struct Flattener {
             size_t cnt[NB] = {};
             for (auto& x : bb) x = Box3::empty();
             for (size_t i = b; i < e; ++i) {
-                int bin = (int)((it[i].c[k] - cmin[k]) / ext * NB);
-                bin = bin < 0 ? 0 : (bin >= NB ? NB - 1 : bin);
+                const int bin = sah_bin(it[i].c[k], cmin[k], ext);
                 bb[bin] = bb[bin].unite(it[i].box);
                 ++cnt[bin];
             }
@@ -433,24 +491,41 @@ struct Flattener {
                 n += cnt[i];
                 if (n == 0 || right_cnt[i + 1] == 0) continue;
                 double cost = half_area(acc) * (double)n + right_area[i + 1] * (double)right_cnt[i + 1];
-                if (cost < best) {
-                    best = cost;
-                    best_axis = k;
-                    best_bin = i;
+                if (cost < best.cost) {
+                    best.cost = cost;
+                    best.axis = k;
+                    best.bin = i;
+                    best.cmin = cmin[k];
+                    best.ext = ext;
                 }
             }
         }
-        if (best_axis >= 0) {
-            const int k = best_axis;
-            const double ext = cmax[k] - cmin[k];
-            auto pivot = std::stable_partition(it.begin() + b, it.begin() + e, [&](const Item& x) {
-                int bin = (int)((x.c[k] - cmin[k]) / ext * NB);
-                bin = bin < 0 ? 0 : (bin >= NB ? NB - 1 : bin);
-                return bin <= best_bin;
-            });
-            mid = (size_t)(pivot - it.begin());
-            if (mid == b || mid == e) mid = b + (e - b) / 2;
+        return best;
+    }
+    // Reorders items[b, e) by the split; returns where the right half starts
+    // (the median when the split separates nothing).
+    static size_t apply_split(std::vector<Item>& it, size_t b, size_t e, const Split& sp) {
+        size_t mid = b + (e - b) / 2;
+        if (sp.axis < 0) return mid;
+        if (!sp.left.empty()) {
+            std::vector<Item> l, r;
+            for (size_t i = b; i < e; ++i) (sp.left[i - b] ? l : r).push_back(it[i]);
+            std::copy(l.begin(), l.end(), it.begin() + b);
+            std::copy(r.begin(), r.end(), it.begin() + b + l.size());
+            return b + l.size();  // (a sweep split has items on both sides)
         }
+        const int k = sp.axis;
+        auto pivot = std::stable_partition(it.begin() + b, it.begin() + e,
+                                           [&](const Item& x) { return sah_bin(x.c[k], sp.cmin, sp.ext) <= sp.bin; });
+        const size_t at = (size_t)(pivot - it.begin());
+        return at == b || at == e ? mid : at;
+    }
+    // SAH build over items[b, e): ranges of at most RT_SAH_SWEEP_MAX items split
+    // by the full sweep, larger ones by the bins.
+    Built sah_build(std::vector<Item>& it, size_t b, size_t e, NodeBuf& nb, int par) {
+        if (e - b == 1) return {it[b].ref, it[b].need, false};
+        const size_t mid =
+            apply_split(it, b, e, e - b <= (size_t)RT_SAH_SWEEP_MAX ? sweep_split(it, b, e) : binned_split(it, b, e));
         const uint32_t idx = (uint32_t)nb.n.size();
         nb.n.emplace_back();
         nb.local.push_back(0);
@@ -1508,10 +1583,27 @@ namespace rth {
 #ifndef RT_BVH4_SPHERES_FIRST
 #define RT_BVH4_SPHERES_FIRST 1
 #endif
+// A/B knobs of the 4-wide collapse: the mesh / full tiers' top-levels-first
+// node order (0: the build's depth-first order), the cost-optimal cut (0: the
+// greedy one)
+#ifndef RT_BVH4_TOP_BFS
+#define RT_BVH4_TOP_BFS 1
+#endif
+#ifndef RT_BVH4_OPTIMAL
+#define RT_BVH4_OPTIMAL 1
+#endif
 
 namespace rth {
 constexpr uint32_t BVH4_TOP = 341;  // 1 + 4 + 16 + 64 + 256
-// Collapses the two-box BVHs of a world into 4-wide nodes: starting from a
+struct Collapsed {  // what a collapse puts in place of the world's two-box trees
+    std::vector<rtk::DNode4> nodes4;
+    std::vector<uint32_t> lists;
+    std::vector<rtk::DXform> xforms;
+    std::vector<rtk::DMedium> media;
+    uint32_t root = 0;
+};
+// Collapses the two-box BVHs of a world into 4-wide nodes.  The greedy collapse:
+// starting from a
 // node's two children, the inner child with the largest box (surface area) is
 // replaced by its own children until there are four or no inner child is left
 // (the usual top-down BVH2 -> BVH4 collapse).  Child boxes are the parents' f32
@@ -1521,7 +1613,24 @@ constexpr uint32_t BVH4_TOP = 341;  // 1 + 4 + 16 + 64 + 256
 // children - 1) + max need(inner child); otherwise (mesh tier) a sphere child
 // gets its box rounded outward and, like every child, is walked near-first
 // through the stack: need(node) = (children - 1) + max need(child).
-uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, size_t max_nodes) {
+//
+// Which descendants of a two-box node x become the children of its 4-wide node
+// -- the cut -- is chosen for the least expected walk cost of the whole tree
+// (optimal = true), with A a box's half area, a visit of a 4-wide node costing
+// 1 and a primitive's test 1:
+//   B(x, 1) = A(x) + B4(x)                      x alone fills one slot
+//   B(x, k) = min(B(x, 1), S(x, k))             x's subtree in up to k slots
+//   S(x, k) = min over i of B(l, i) + B(r, k - i),   B4(x) = S(x, 4)
+//   B(p, k) = A(p)                              p a primitive
+// in post-order over the two-box nodes, the cut read back from the minima; a
+// cut that costs what the greedy one does gives way to it.  (Every primitive
+// fills one slot under any cut, so a primitive's weight does not matter: the
+// sum that is minimised is the area of all inner 4-wide nodes.)  optimal =
+// false is the greedy collapse alone.
+// Returns the tree's stack need with `res` filled, or with `res` empty: a need
+// above max_need, or UINT32_MAX for more than max_nodes nodes.
+static uint32_t bvh4_collapse(const HostWorld& hw, uint32_t max_need, bool filter_spheres, size_t max_nodes, bool optimal,
+                              Collapsed& res) {
     using rtk::REF_NONE;
     struct Child {
         uint32_t ref;
@@ -1553,7 +1662,6 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
             Child c{};
             c.ref = refs[k];
             if (rtk::ref_kind(refs[k]) == rtk::K_SPHERE) {
-                c.area = -1.0;
                 const double* sp = n.slot[k].sphere;
                 for (int a = 0; a < 3; ++a) {
                     c.lo[a] = round_down(sp[a] - sp[3]);
@@ -1564,16 +1672,16 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
                     c.lo[a] = n.slot[k].box.lo[a];
                     c.hi[a] = n.slot[k].box.hi[a];
                 }
-                const double dx = std::fmax((double)c.hi[0] - c.lo[0], 0.0), dy = std::fmax((double)c.hi[1] - c.lo[1], 0.0),
-                             dz = std::fmax((double)c.hi[2] - c.lo[2], 0.0);
-                c.area = dx * dy + dy * dz + dz * dx;
             }
+            const double dx = std::fmax((double)c.hi[0] - c.lo[0], 0.0), dy = std::fmax((double)c.hi[1] - c.lo[1], 0.0),
+                         dz = std::fmax((double)c.hi[2] - c.lo[2], 0.0);
+            c.area = dx * dy + dy * dz + dz * dx;
             v.push_back(c);
         }
     };
-    std::function<uint32_t(uint32_t)> conv = [&](uint32_t idx) -> uint32_t {
-        if (map[idx] != REF_NONE) return map[idx];
-        std::vector<Child> ch;
+    // today's greedy cut: the inner child with the largest box is replaced by
+    // its own children until there are four or no inner child is left
+    auto greedy_cut = [&](uint32_t idx, std::vector<Child>& ch) {
         kids(idx, ch);
         for (;;) {
             if (ch.size() >= 4) break;
@@ -1585,6 +1693,90 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
             kids(rtk::ref_index(ch[best].ref), sub);
             ch.erase(ch.begin() + best);
             ch.insert(ch.begin() + best, sub.begin(), sub.end());
+        }
+    };
+    // S(x, 2 .. 4) of every two-box node (index k - 2), children before parents
+    struct Cost {
+        double s[3];
+    };
+    std::vector<Cost> S;
+    auto B = [&](const Child& c, int k) -> double {
+        if (rtk::ref_kind(c.ref) != rtk::K_BVH) return c.area;
+        const Cost& x = S[rtk::ref_index(c.ref)];
+        const double one = c.area + x.s[2];
+        return k == 1 ? one : std::fmin(one, x.s[k - 2]);
+    };
+    if (optimal) {
+        S.assign(hw.nodes.size(), Cost{{0.0, 0.0, 0.0}});
+        std::vector<uint8_t> state(hw.nodes.size(), 0);  // 1: children pushed, 2: done
+        std::vector<uint32_t> todo;
+        std::vector<Child> ch;
+        for (uint32_t seed = 0; seed < (uint32_t)hw.nodes.size(); ++seed) {
+            if (state[seed]) continue;
+            todo.push_back(seed);
+            while (!todo.empty()) {
+                const uint32_t x = todo.back();
+                if (state[x] == 2) {
+                    todo.pop_back();
+                    continue;
+                }
+                ch.clear();
+                kids(x, ch);
+                if (state[x] == 0) {
+                    state[x] = 1;
+                    for (const Child& c : ch)
+                        if (rtk::ref_kind(c.ref) == rtk::K_BVH && state[rtk::ref_index(c.ref)] == 0)
+                            todo.push_back(rtk::ref_index(c.ref));
+                    continue;
+                }
+                for (int k = 2; k <= 4; ++k) {
+                    double best = 0.0;
+                    if (ch.size() == 1) best = B(ch[0], k);
+                    for (int i = 1; ch.size() == 2 && i < k; ++i) {
+                        const double v = B(ch[0], i) + B(ch[1], k - i);
+                        if (i == 1 || v < best) best = v;
+                    }
+                    S[x].s[k - 2] = best;
+                }
+                state[x] = 2;
+                todo.pop_back();
+            }
+        }
+    }
+    // the cut of least cost below two-box node idx, in up to k slots, left to right
+    std::function<void(uint32_t, int, std::vector<Child>&)> optimal_cut = [&](uint32_t idx, int k, std::vector<Child>& out_ch) {
+        std::vector<Child> ch;
+        kids(idx, ch);
+        int take[2] = {k, 0};
+        if (ch.size() == 2) {
+            take[0] = 1;
+            for (int i = 2; i < k; ++i)
+                if (B(ch[0], i) + B(ch[1], k - i) < B(ch[0], take[0]) + B(ch[1], k - take[0])) take[0] = i;
+            take[1] = k - take[0];
+        }
+        for (size_t j = 0; j < ch.size(); ++j) {  // (at most three levels deep: k shrinks)
+            const Child& c = ch[j];
+            if (rtk::ref_kind(c.ref) != rtk::K_BVH || take[j] == 1 ||
+                c.area + S[rtk::ref_index(c.ref)].s[2] <= S[rtk::ref_index(c.ref)].s[take[j] - 2])
+                out_ch.push_back(c);
+            else
+                optimal_cut(rtk::ref_index(c.ref), take[j], out_ch);
+        }
+    };
+    auto cut_cost = [&](const std::vector<Child>& ch) {
+        double v = 0.0;
+        for (const Child& c : ch) v += B(c, 1);
+        return v;
+    };
+    std::function<uint32_t(uint32_t)> conv = [&](uint32_t idx) -> uint32_t {
+        if (map[idx] != REF_NONE) return map[idx];
+        std::vector<Child> ch;
+        greedy_cut(idx, ch);
+        if (optimal) {
+            std::vector<Child> best;
+            optimal_cut(idx, 4, best);
+            // (equal up to the rounding of two orders of summation: the greedy cut)
+            if (cut_cost(best) < cut_cost(ch) * (1.0 - 0x1p-40)) ch.swap(best);
         }
 #if RT_BVH4_SPHERES_FIRST
         // basic tier: sphere children in the low slots, boxes after them, empty
@@ -1673,10 +1865,9 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
     const uint32_t sn = 1 + need(root);
     if (sn > max_need) return sn;
     if (out.size() > max_nodes) return UINT32_MAX;
-    // (RT_BVH4_TOP_BFS=0: the build's depth-first order throughout -- an A/B
-    // knob of the layout, read from the environment like rt_render.cpp's)
-    const char* bfs_env = std::getenv("RT_BVH4_TOP_BFS");
-    if (!filter_spheres && !(bfs_env && bfs_env[0] == '0')) {
+    // (-DRT_BVH4_TOP_BFS=0: the build's depth-first order throughout -- an A/B
+    // knob of the layout)
+    if (!filter_spheres && RT_BVH4_TOP_BFS) {
         // the mesh / full tiers: the first BVH4_TOP nodes breadth-first from the
         // world's root BVH (levels 0-4 of a full 4-wide tree) take indices
         // 0 .. BVH4_TOP - 1, the rest keep the build's depth-first order after
@@ -1715,12 +1906,41 @@ uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, siz
         for (rtk::DMedium& m : media) remap(m.boundary);
         remap(root);
     }
-    hw.nodes4 = std::move(out);
+    res.nodes4 = std::move(out);
+    res.lists = std::move(lists);
+    res.xforms = std::move(xforms);
+    res.media = std::move(media);
+    res.root = root;
+    return sn;
+}
+
+// The cost-optimal collapse, unless the greedy one keeps a world where the
+// optimal one would move it: where the optimal tree needs more stack than
+// max_need or more nodes than max_nodes and the greedy tree does not (no world
+// moves up a tier for the choice of cut), and where the two trees' node counts
+// lie on different sides of variant_nodes (no world changes its kernel variant
+// for it either).
+uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, size_t max_nodes, size_t variant_nodes) {
+    Collapsed best;
+    uint32_t sn = bvh4_collapse(hw, max_need, filter_spheres, max_nodes, RT_BVH4_OPTIMAL != 0, best);
+#if RT_BVH4_OPTIMAL
+    if (sn > max_need || variant_nodes) {
+        Collapsed greedy;
+        const uint32_t sg = bvh4_collapse(hw, max_need, filter_spheres, max_nodes, false, greedy);
+        if (sn > max_need ||
+            (sg <= max_need && variant_nodes && (greedy.nodes4.size() > variant_nodes) != (best.nodes4.size() > variant_nodes))) {
+            sn = sg;
+            best = std::move(greedy);
+        }
+    }
+#endif
+    if (sn > max_need) return sn;
+    hw.nodes4 = std::move(best.nodes4);
     hw.nodes.clear();  // the two-box nodes are not walked any more
-    hw.list_children = std::move(lists);
-    hw.xforms = std::move(xforms);
-    hw.media = std::move(media);
-    hw.world_root = root;
+    hw.list_children = std::move(best.lists);
+    hw.xforms = std::move(best.xforms);
+    hw.media = std::move(best.media);
+    hw.world_root = best.root;
     hw.stack_need = sn;
     return sn;
 }

@@ -5,7 +5,8 @@
 // and the reference BVH topology are computed exactly as the reference does
 // (aabb.rs, bvh.rs:16-46, shapes.rs:49-72).  `flatten` turns one (world,
 // lights) pair into the device layout of rt_layout.h; by default it rebuilds
-// every BVH with a binned SAH over the same objects (tight boxes), keeping the
+// every BVH with a SAH build (a full sweep over small ranges, 32 bins an axis
+// over large ones) over the same objects (tight boxes), keeping the
 // reference topology only on request (RT_FLAG_REFERENCE_BVH).
 #pragma once
 #include <cmath>
@@ -154,7 +155,7 @@ namespace rth {
 int32_t set_error(int32_t code, const std::string& msg);
 // Flattens (world, lights) of scene s; lights = -1 for None.  Returns RT_OK or an RT_E* code.
 // reference_bvh: keep the reference's BVH topology (bvh.rs:16-46) instead of
-// the binned-SAH rebuild (closest-hit results agree up to exact t ties).
+// the SAH rebuild (closest-hit results agree up to exact t ties).
 int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, bool reference_bvh,
                 HostWorld& out);
 // Collapses every two-box BVH into 4-wide nodes (hw.nodes4; sphere children with
@@ -162,7 +163,12 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
 // tier), rewrites the K_BVH refs
 // to index nodes4 and recomputes stack_need.  Returns the new stack_need (hw is
 // unchanged when it exceeds max_need), or UINT32_MAX (hw unchanged) when the
-// tree would have more than max_nodes nodes.
-uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, size_t max_nodes = SIZE_MAX);
+// tree would have more than max_nodes nodes.  The children of a 4-wide node are
+// the cut of least expected walk cost; the greedy cut (largest inner child
+// first) decides where the optimal tree would not fit max_need / max_nodes and
+// the greedy one does, and, with variant_nodes set, where the two trees' node
+// counts lie on different sides of it (the caller's kernel variants).
+uint32_t bvh4_convert(HostWorld& hw, uint32_t max_need, bool filter_spheres, size_t max_nodes = SIZE_MAX,
+                      size_t variant_nodes = 0);
 void destroy_render_state(RenderState* r);
 }  // namespace rth
