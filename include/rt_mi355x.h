@@ -290,6 +290,33 @@ int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, 
 int32_t rt_world_hit_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_device,
                             uint64_t n, rt_hit_record* out_device, void* stream);
 
+/* ---- Occlusion queries: is anything in the way ----------------------------- */
+/* world.hit(Ray{origin, dir, time}, [1e-8, t_max]).is_some() (hit.rs:46-60)
+ * for each of n rays -- the any-hit query of shadow rays, visibility tests
+ * and ambient occlusion, which need no record: the walk ends at the first
+ * accepted hit and one byte a ray comes back.  The contract: for the same
+ * (world, seed, flags, rays, index),
+ *     out[i] == ((record[i].flags & RT_HIT_FOUND) != 0)
+ * of rt_world_hit -- 1 or 0, nothing else.  A ConstantMedium hit occludes, as
+ * hit returning Some does, and its draw is rt_world_hit's: the medium stream
+ * of (seed, pixel = the ray's index, sample 0, vertex 1).
+ * A segment test from a to b is the ray origin = a, dir = b - a with t_max
+ * just under 1 (b itself, when it lies on a surface, is then not in the way):
+ * that is what t_max is on the ray for.
+ * Everything else is rt_world_hit's: the argument checks and error codes (the
+ * host variant validates every ray), n == 0 (RT_OK, no device touched, no
+ * arrays needed), n < 2^32, flags, the flattening and the scene's per-device
+ * world cache -- a render, a hit query and an occlusion query of one
+ * flattening upload it once -- and the ordering after the scene's previous
+ * device work.  Host arrays, blocking: */
+int32_t rt_world_occluded(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                          uint8_t* out);
+/* The same from and to gfx950 device arrays, enqueued on `stream` without
+ * waiting, as rt_world_hit_device: the rays are the caller's duty, and the
+ * kernel ends and writes a byte for any ray, and none past out_device[n - 1]. */
+int32_t rt_world_occluded_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_device,
+                                 uint64_t n, uint8_t* out_device, void* stream);
+
 /* Number of rows a shard renders (rows of the compact output). */
 uint32_t rt_shard_rows(const rt_camera* cam, const rt_render_opts* opts);
 

@@ -147,6 +147,8 @@ SIGNATURES = {
                     C.POINTER(C.c_uint8), C.POINTER(RtStats)]),
     "world_hit": (_I, [_P, _I, C.c_uint64, _U, C.POINTER(RtRay), C.c_uint64, C.POINTER(RtHitRecord)]),
     "world_hit_device": (_I, [_P, _I, C.c_uint64, _U, _P, C.c_uint64, _P, _P]),
+    "world_occluded": (_I, [_P, _I, C.c_uint64, _U, C.POINTER(RtRay), C.c_uint64, C.POINTER(C.c_uint8)]),
+    "world_occluded_device": (_I, [_P, _I, C.c_uint64, _U, _P, C.c_uint64, _P, _P]),
     "shard_rows": (_U, [C.POINTER(RtCamera), C.POINTER(RtRenderOpts)]),
     "render_device": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), _P]),
     "render_device_wait": (_I, [_P, C.POINTER(RtStats)]),
@@ -167,7 +169,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

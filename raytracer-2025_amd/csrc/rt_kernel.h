@@ -1,6 +1,6 @@
 // rt_kernel.h -- interface between the host render driver (rt_render.cpp) and
 // the gfx950 kernels (rt_kernel_path.hip, rt_kernel_hit.hip,
-// rt_kernel_common.hip).
+// rt_kernel_occl.hip, rt_kernel_common.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -155,6 +155,11 @@ struct rt_hit_record;
 extern "C" __attribute__((weak)) hipError_t rtk_launch_hits(const rtk::SceneView* view, const struct rt_ray* rays,
                                                             struct rt_hit_record* out, uint64_t n, uint64_t seed,
                                                             int tier, int grid, void* stack_ovf, hipStream_t stream);
+// rt_world_occluded's kernel: whether world.hit of each of n rays is Some, one
+// byte a ray; grid and weakness as rtk_launch_hits.
+extern "C" __attribute__((weak)) hipError_t rtk_launch_occluded(const rtk::SceneView* view, const struct rt_ray* rays,
+                                                                uint8_t* out, uint64_t n, uint64_t seed, int tier,
+                                                                int grid, void* stack_ovf, hipStream_t stream);
 // device bytes rtk_launch_frame needs at params_dev
 extern "C" size_t rtk_params_bytes(void);
 extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu);

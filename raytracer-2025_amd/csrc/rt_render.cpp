@@ -1065,8 +1065,8 @@ int32_t rt_render_device(rt_scene* s, int32_t world, int32_t lights, const rt_ca
     }
 }
 
-// rt_world_hit's argument checks, shared by both variants; n == 0 is decided
-// by the caller after them
+// The argument checks of rt_world_hit and rt_world_occluded, shared by the
+// variants of both; n == 0 is decided by the caller after them
 static int32_t hit_args(rt_scene* s, int32_t world, uint32_t flags, const void* rays, uint64_t n, const void* out) {
     if (!s) return set_error(RT_EINVAL, "null scene");
     if (flags & ~RT_FLAG_REFERENCE_BVH) return set_error(RT_EINVAL, "unknown flags");
@@ -1074,19 +1074,25 @@ static int32_t hit_args(rt_scene* s, int32_t world, uint32_t flags, const void* 
     if (world < 0 || (size_t)world >= s->objs.size() || s->objs[world].hidden)
         return set_error(RT_EHANDLE, "unknown world handle");
     if (s->objs[world].moved) return set_error(RT_EMOVED, "world handle was moved");
-    if (n && (!rays || !out)) return set_error(RT_EINVAL, "null ray or record array");
+    if (n && (!rays || !out)) return set_error(RT_EINVAL, "null ray or output array");
     return RT_OK;
 }
+
+// What a query writes for a ray: rt_world_hit's record or rt_world_occluded's byte
+enum QueryKind { Q_RECORD, Q_OCCLUDED };
+static size_t query_out_bytes(QueryKind k) { return k == Q_RECORD ? sizeof(rt_hit_record) : sizeof(uint8_t); }
 
 // Enqueues the query on `stream` of the current device: slot 0's device world
 // as a render of (world, no lights, no background) leaves it, after the
 // slot's previous work.
 static int32_t hit_enqueue(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
-                           uint64_t n, rt_hit_record* out_dev, hipStream_t stream) {
+                           uint64_t n, QueryKind kind, void* out_dev, hipStream_t stream) {
     int cur = -1;
     hipError_t e = hipGetDevice(&cur);
     if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
-    if (!rtk_launch_hits) return set_error(RT_EUNSUPPORTED, "this build holds no hit-query kernels");
+    if (kind == Q_RECORD && !rtk_launch_hits) return set_error(RT_EUNSUPPORTED, "this build holds no hit-query kernels");
+    if (kind == Q_OCCLUDED && !rtk_launch_occluded)
+        return set_error(RT_EUNSUPPORTED, "this build holds no occlusion-query kernels");
     if (!s->rs) s->rs = new RenderState();
     RenderState* r = s->rs;
     if (r->slots.empty()) r->slots.resize(1, nullptr);
@@ -1104,27 +1110,32 @@ static int32_t hit_enqueue(rt_scene* s, int32_t world, uint64_t seed, uint32_t f
         return hip_fail(e, "hipStreamWaitEvent");
     if (r->g_recorded && (e = hipStreamWaitEvent(stream, r->g_stop, 0)) != hipSuccess)
         return hip_fail(e, "hipStreamWaitEvent");
-    if ((e = rtk_launch_hits(&d->view, rays_dev, out_dev, n, seed, d->tier, d->grid[d->tier], d->stack_ovf, stream)) !=
-        hipSuccess)
-        return hip_fail(e, "hit kernel launch");
+    e = kind == Q_RECORD ? rtk_launch_hits(&d->view, rays_dev, (rt_hit_record*)out_dev, n, seed, d->tier,
+                                           d->grid[d->tier], d->stack_ovf, stream)
+                         : rtk_launch_occluded(&d->view, rays_dev, (uint8_t*)out_dev, n, seed, d->tier,
+                                               d->grid[d->tier], d->stack_ovf, stream);
+    if (e != hipSuccess) return hip_fail(e, kind == Q_RECORD ? "hit kernel launch" : "occlusion kernel launch");
     if ((e = hipEventRecord(d->ev_done, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
     d->done_recorded = true;
     return RT_OK;
 }
 
-int32_t rt_world_hit_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
-                            uint64_t n, rt_hit_record* out_dev, void* stream) {
+// The device variant of either query
+static int32_t query_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
+                            uint64_t n, QueryKind kind, void* out_dev, void* stream) {
     const int32_t rc = hit_args(s, world, flags, rays_dev, n, out_dev);
     if (rc != RT_OK || n == 0) return rc;
     try {
-        return hit_enqueue(s, world, seed, flags, rays_dev, n, out_dev, (hipStream_t)stream);
+        return hit_enqueue(s, world, seed, flags, rays_dev, n, kind, out_dev, (hipStream_t)stream);
     } catch (const std::bad_alloc&) {
         return set_error(RT_ENOMEM, "out of host memory");
     }
 }
 
-int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
-                     rt_hit_record* out) {
+// The host variant of either query: the rays validated, then through device
+// copies on the default stream, blocking
+static int32_t query_host(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                          QueryKind kind, void* out) {
     int32_t rc = hit_args(s, world, flags, rays, n, out);
     if (rc != RT_OK || n == 0) return rc;
     for (uint64_t i = 0; i < n; ++i) {
@@ -1137,21 +1148,21 @@ int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, 
                                             ": non-finite origin, direction or time, zero direction, or NaN / negative t_max");
     }
     char* buf = nullptr;
-    const size_t ray_bytes = (size_t)n * sizeof(rt_ray), out_bytes = (size_t)n * sizeof(rt_hit_record);
+    const size_t ray_bytes = (size_t)n * sizeof(rt_ray), out_bytes = (size_t)n * query_out_bytes(kind);
     hipError_t e = hipMalloc((void**)&buf, ray_bytes + out_bytes);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc rays");
-    rt_hit_record* out_dev = (rt_hit_record*)(buf + ray_bytes);
+    void* out_dev = buf + ray_bytes;
     if ((e = hipMemcpy(buf, rays, ray_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
         rc = hip_fail(e, "hipMemcpy rays");
     } else {
         try {
-            rc = hit_enqueue(s, world, seed, flags, (const rt_ray*)buf, n, out_dev, nullptr);
+            rc = hit_enqueue(s, world, seed, flags, (const rt_ray*)buf, n, kind, out_dev, nullptr);
         } catch (const std::bad_alloc&) {
             rc = set_error(RT_ENOMEM, "out of host memory");
         }
-        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "hit query (stream synchronize)");
+        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "query (stream synchronize)");
         if (rc == RT_OK && (e = hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
-            rc = hip_fail(e, "hipMemcpy records");
+            rc = hip_fail(e, "hipMemcpy results");
         if (rc == RT_OK && rtk_check_read) {  // check build: refs past their arrays, as a render reports them
             unsigned long long c[2] = {0, 0};
             if ((e = (hipError_t)rtk_check_read(c, 1)) != hipSuccess)
@@ -1165,6 +1176,26 @@ int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, 
     }
     (void)hipFree(buf);
     return rc;
+}
+
+int32_t rt_world_hit_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
+                            uint64_t n, rt_hit_record* out_dev, void* stream) {
+    return query_device(s, world, seed, flags, rays_dev, n, Q_RECORD, out_dev, stream);
+}
+
+int32_t rt_world_hit(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                     rt_hit_record* out) {
+    return query_host(s, world, seed, flags, rays, n, Q_RECORD, out);
+}
+
+int32_t rt_world_occluded_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_dev,
+                                 uint64_t n, uint8_t* out_dev, void* stream) {
+    return query_device(s, world, seed, flags, rays_dev, n, Q_OCCLUDED, out_dev, stream);
+}
+
+int32_t rt_world_occluded(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
+                          uint8_t* out) {
+    return query_host(s, world, seed, flags, rays, n, Q_OCCLUDED, out);
 }
 
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t bg, uint32_t flags, rt_world_info* out) {

@@ -219,6 +219,30 @@ class Scene:
         self._c(self.api.world_hit_device(self.s, world.h, int(seed), int(flags), C.c_void_p(int(rays_ptr)), int(n),
                                           C.c_void_p(int(out_ptr)), C.c_void_p(stream) if stream else None))
 
+    # ---- Hittable::hit(..).is_some(): any-hit queries (shadow rays, visibility, ambient occlusion)
+    def occluded(self, world, rays, seed=0, flags=0):
+        """Whether world.hit(Ray{origin, dir, time}, [1e-8, t_max]) is Some for
+        each row of the (n, 8) float64 array `rays`, as `hit` takes them
+        (rt_world_occluded).  Returns an (n,) uint8 array of 0 / 1: the
+        RT_HIT_FOUND bit of the record `hit` returns for that ray.  A segment
+        test from a to b is the ray (a, b - a) with t_max just under 1."""
+        a = np.ascontiguousarray(rays, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) array: origin, direction, time, t_max")
+        n = a.shape[0]
+        out = np.zeros(n, dtype=np.uint8)
+        self._c(self.api.world_occluded(self.s, world.h, int(seed), int(flags), a.ctypes.data_as(C.POINTER(RtRay)), n,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def occluded_device(self, world, rays_ptr, n, out_ptr, seed=0, flags=0, stream=None):
+        """rt_world_occluded_device: n rt_ray at the device address rays_ptr, n
+        bytes written at out_ptr, enqueued on `stream` (a hipStream_t as an
+        integer; None = the default stream) without waiting."""
+        self._c(self.api.world_occluded_device(self.s, world.h, int(seed), int(flags), C.c_void_p(int(rays_ptr)),
+                                               int(n), C.c_void_p(int(out_ptr)),
+                                               C.c_void_p(stream) if stream else None))
+
 
 class Camera:
     """camera.rs:45-104 -- pub fields with Camera::default values."""
