@@ -103,6 +103,24 @@ int32_t rt_mat_mix(rt_scene* s, int32_t mat1, int32_t mat2, double ratio); /* Mi
 /* Mix::from_image (material.rs:235-247): ratio = the image texture's alpha at
  * (u, v) (ImageTexture::alpha, texture.rs:99-106: 1 for a missing image) */
 int32_t rt_mat_mix_image(rt_scene* s, int32_t mat1, int32_t mat2, int32_t image_tex);
+/* DisneyParameters (material/disney.rs:17-34) without base_color */
+typedef struct rt_disney_params {
+    uint32_t struct_size; /* sizeof(rt_disney_params) as the caller compiled it; as
+                           * rt_render_opts: fields are only ever appended */
+    int32_t thin;
+    double roughness, anisotropic, sheen, sheen_tint, clearcoat, clearcoat_gloss, specular_tint, metallic, ior, flatness,
+        spec_trans, diff_trans;
+} rt_disney_params;
+/* DisneyParameters::default (disney.rs:36-55) */
+void rt_disney_params_default(rt_disney_params* params);
+/* Disney { param_fn: |u, v, p| DisneyParameters { base_color: tex.value(u, v, p), ..params } }
+ * (disney.rs:59-61): Disney::builder()...build() with a SolidColor, and the
+ * closure of obj.rs:279-292 with any texture.  RT_EHANDLE: unknown texture;
+ * RT_EINVAL: null pointer, a struct_size below this version's, a non-finite
+ * field.  Ranges are not checked, as the reference checks none: a parameter
+ * set that makes NaNs is counted in rt_stats.panics like every other
+ * reference assert. */
+int32_t rt_mat_disney(rt_scene* s, int32_t base_color_tex, const rt_disney_params* params);
 
 /* ---- Hittables ------------------------------------------------------------ */
 /* Sphere::new (shapes/sphere.rs:25-35) */
@@ -230,7 +248,9 @@ typedef struct rt_world_info {
     uint32_t primitives;      /* spheres + moving spheres + quads + triangles */
     uint32_t bvh_leaves;      /* objects under BVHs */
     uint32_t stack_need;      /* traversal-stack entries one lane needs */
-    uint32_t kernel_tier;     /* 0 = spheres/BVH/basic materials, 1 = + quads/triangles/OBJ, 2 = full */
+    uint32_t kernel_tier;     /* 0 = spheres/BVH/basic materials, 1 = + quads/triangles/OBJ, 2 = full,
+                               * 3 = full without BVH nodes, 4 = full + general lights / nested
+                               * wrapper materials, 5 = 4 + the Disney BSDF (rt_kernel.h Tier) */
     uint32_t features;        /* F_* bits (rt_layout.h) */
 } rt_world_info;
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, uint32_t flags,
@@ -357,7 +377,8 @@ int32_t rt_render_partials_get(rt_scene* s, double* out, uint64_t n_values);
  * one f64 function on the current gfx950 device, from host arrays a (and b)
  * into out.  fn: 0 sin, 1 cos, 2 sincos's sin, 3 sincos's cos, 4 log (ln),
  * 5 acos, 6 atan2(a, b), 7 sqrt, 8 / 9 sin / cos of 2 pi a (a a unit draw,
- * the path's sincos_2pi).  impl 0: the functions the render kernel
+ * the path's sincos_2pi), 10 0.0625^a for a in [0, 1] (rtcr::pow_2m4, the
+ * clearcoat sampler's powf; impl 1: ocml's pow).  impl 0: the functions the render kernel
  * calls (rt_crmath.h: correctly rounded, in place of Rust's f64::sin / cos /
  * ln / acos / atan2 = glibc's); impl 1: ROCm's device libm (ocml).  Blocking. */
 int32_t rt_math_selftest(int32_t fn, int32_t impl, const double* a, const double* b, double* out, uint64_t n);
@@ -376,6 +397,22 @@ int32_t rt_math_selftest(int32_t fn, int32_t impl, const double* a, const double
  *   6  the largest f32 <= x: x -> r
  * Blocking. */
 int32_t rt_walk_selftest(int32_t fn, const double* in, double* out, uint64_t n);
+
+/* Test hook (parity tooling, not part of the reference surface): n cases of
+ * the Disney BSDF's device functions as the path kernel's tier 5 compiles
+ * them, on the current gfx950 device, for one parameter set and base colour;
+ * host arrays, a fixed number of doubles per case.  fn:
+ *   0  Disney::evaluate_disney (disney.rs:289-401): v_out[3], v_in[3] (both in
+ *      the shading frame, y = the normal), front_face (0 / 1) ->
+ *      reflectance[3], forward pdf, reverse pdf, panic (0 / 1)
+ *   1  Disney::scatter's v_out, DisneyPDF::new and generate (disney.rs:77,
+ *      524-540, 672-690) with the draws given instead of drawn: world
+ *      normal[3], world -r_in.direction[3], front_face, four unit draws in call
+ *      order -> 1 / 0 (Some / None), direction[3], draws consumed, panic
+ * A case that panics (a reference unwrap / expect / assert!) is zeros and the
+ * flag.  RT_EUNSUPPORTED in a build without the kernels.  Blocking. */
+int32_t rt_disney_selftest(int32_t fn, const rt_disney_params* params, const double base_color[3], const double* in,
+                           double* out, uint64_t n);
 
 /* Test hook (host only, not part of the reference surface): builds
  * BVH::from_vec (bvh.rs:16-46) over the children of `list` twice, on copies

@@ -43,6 +43,14 @@ class RtWorldInfo(C.Structure):
     ]
 
 
+class RtDisneyParams(C.Structure):
+    """rt_disney_params -- DisneyParameters (material/disney.rs:17-34) without base_color."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("thin", C.c_int32)] + [(n, C.c_double) for n in (
+        "roughness", "anisotropic", "sheen", "sheen_tint", "clearcoat", "clearcoat_gloss", "specular_tint", "metallic",
+        "ior", "flatness", "spec_trans", "diff_trans")]
+
+
 class RtRenderOpts(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -127,6 +135,8 @@ SIGNATURES = {
     "mat_transparent": (_I, [_P]),
     "mat_mix": (_I, [_P, _I, _I, _D]),
     "mat_mix_image": (_I, [_P, _I, _I, _I]),
+    "disney_params_default": (None, [C.POINTER(RtDisneyParams)]),
+    "mat_disney": (_I, [_P, _I, C.POINTER(RtDisneyParams)]),
     "sphere": (_I, [_P, _DP, _D, _I]),
     "sphere_moving": (_I, [_P, _DP, _DP, _D, _I]),
     "quad": (_I, [_P, _DP, _DP, _DP, _I]),
@@ -160,6 +170,7 @@ SIGNATURES = {
     "render_partials_get": (_I, [_P, _DP, C.c_uint64]),
     "math_selftest": (_I, [_I, _I, _DP, _DP, _DP, C.c_uint64]),
     "walk_selftest": (_I, [_I, _DP, _DP, C.c_uint64]),
+    "disney_selftest": (_I, [_I, C.POINTER(RtDisneyParams), _DP, _DP, _DP, C.c_uint64]),
     "bvh_selftest": (_I, [_P, _I]),
     "world_selftest": (_I, [_P, _I, _I, _I]),
     "comm_unique_id": (_I, [C.POINTER(C.c_uint8)]),
@@ -169,7 +180,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -1,5 +1,6 @@
-// rt_crmath.h -- correctly rounded f64 sin, cos, sincos, log, atan2, acos,
-// one source for the gfx950 kernel and for host code (g++ / hipcc host pass).
+// rt_crmath.h -- correctly rounded f64 sin, cos, sincos, log, atan2, acos and
+// 0.0625^y (pow_2m4), one source for the gfx950 kernel and for host code (g++ /
+// hipcc host pass).
 //
 // Why: the reference calls Rust's f64::sin / cos / ln / acos / atan2, which on
 // Linux are glibc's libm.  ROCm's ocml versions differ from glibc
@@ -605,6 +606,57 @@ RTCR_FN double acos(double y) {
     double r;
     if (!atan_core(n, DD{ay, 0.0}, xneg, false, r)) atan_core(n, DD{ay, 0.0}, xneg, true, r);
     return r;
+}
+
+// ------------------------------------------------------------------ pow_2m4
+// 0.0625^y = 2^(-4 y) for y in [0, 1] (NaN outside): the clearcoat sampler's
+// a2.powf(1 - r0) with a2 = 0.0625 (disney.rs:568).  t = -4 y is exact; t =
+// n + j/32 + r with n = floor, 0 <= j < 32 and |r| <= 1/64 exact, and 2^t =
+// 2^n T[j] exp(r ln 2) with T[j] = 2^(j/32) from RTCR_EXP2_T; the scale by
+// 2^n (n in -4 .. 0) is exact.  y = k/4 gives r = 0, j = 0: the exact power.
+RTCR_SLOW double pow_2m4_slow(double r, int j, double scale) {
+    RTCR_NOCONTRACT
+    RTCR_COUNT_SLOW();
+    const DD x = dd_mul_d(DD{RTCR_LN2D_H, RTCR_LN2D_L}, r);  // |x| < 0.0109
+    // exp(x) = 1 + x (1 + x/2! + ... + x^12/13!): the next term is below 2^-126
+    DD acc{RTCR_IFACT[13][0], RTCR_IFACT[13][1]};
+    for (int k = 12; k >= 1; --k) acc = dd_add(DD{RTCR_IFACT[k][0], RTCR_IFACT[k][1]}, dd_mul(x, acc));
+    const DD e = dd_add(DD{1.0, 0.0}, dd_mul(x, acc));
+    const DD y = dd_mul(DD{RTCR_EXP2_T[j][0], RTCR_EXP2_T[j][1]}, e);
+    return (y.h + y.l) * scale;
+}
+
+RTCR_FN double pow_2m4(double y) {
+    RTCR_NOCONTRACT
+    if (!(y >= 0.0 && y <= 1.0)) return (y - y) / (y - y);
+    const double t = -4.0 * y;
+    const double kf = __builtin_rint(t * 32.0);  // -128 .. 0
+    const int k = (int)kf;
+    const double r = t - kf * 0.03125;  // exact: the low bits of t
+    const int j = k & 31;
+    const double scale = from_bits((uint64_t)(1023 + ((k - j) >> 5)) << 52);
+    // x = r ln 2 as a double-double
+    DD x = two_prod(r, RTCR_LN2D_H);
+    x.l = fma_(r, RTCR_LN2D_L, x.l);
+    const double xh = x.h;
+    // exp(x) = 1 + x + x^2/2 + x^3 (1/3! + x/4! + ... + x^7/10!): next term < 2^-97
+    const DD s = two_prod(xh, xh);
+    double P = RTCR_IFACT[10][0];
+    for (int i = 9; i >= 3; --i) P = fma_(xh, P, RTCR_IFACT[i][0]);
+    const double p3 = (xh * s.h) * P;
+    const DD a = fast_two_sum(1.0, xh);
+    const DD b = two_sum(a.h, 0.5 * s.h);
+    double lo = ((a.l + b.l) + x.l) + 0.5 * s.l;
+    lo = fma_(xh, x.l, lo);
+    lo += p3;
+    const DD e = fast_two_sum(b.h, lo);
+    const double th = RTCR_EXP2_T[j][0], tl = RTCR_EXP2_T[j][1];
+    DD v = two_prod(th, e.h);
+    v.l = fma_(th, e.l, fma_(tl, e.h, v.l));
+    v = fast_two_sum(v.h, v.l);
+    const double err = fma_(abs_(p3), 0x1p-48, 0x1p-90);
+    if (rounds_ok(v.h, v.l, err)) return v.h * scale;
+    return pow_2m4_slow(r, j, scale);
 }
 
 }  // namespace rtcr

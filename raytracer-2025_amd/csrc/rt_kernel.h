@@ -61,11 +61,15 @@ namespace rtk {
 //  FULL_GL: FULL with general lights (Transforms, nested lists, moving
 //         spheres in the lights tree); kept apart so that the light-tree
 //         code does not weigh on the C3 / C5 tiers.
-enum Tier : int { TIER_BASIC = 0, TIER_MESH = 1, TIER_FULL = 2, TIER_FULL_FLAT = 3, TIER_FULL_GL = 4 };
-constexpr int N_TIERS = 5;
+//  FULL_DS: FULL_GL with the Disney BSDF (rt_disney.h): the one tier whose
+//         shade() holds M_DISNEY, so that no other tier pays for it.
+enum Tier : int { TIER_BASIC = 0, TIER_MESH = 1, TIER_FULL = 2, TIER_FULL_FLAT = 3, TIER_FULL_GL = 4, TIER_FULL_DS = 5 };
+constexpr int N_TIERS = 6;
+// tiers with FULL_GL's general lights and wrapper materials
+__host__ __device__ constexpr bool tier_general(int t) { return t == TIER_FULL_GL || t == TIER_FULL_DS; }
 __host__ __device__ constexpr bool tier_full(int t) { return t >= TIER_FULL; }
 // full tiers that walk BVH nodes
-__host__ __device__ constexpr bool tier_full_bvh(int t) { return t == TIER_FULL || t == TIER_FULL_GL; }
+__host__ __device__ constexpr bool tier_full_bvh(int t) { return t == TIER_FULL || t == TIER_FULL_GL || t == TIER_FULL_DS; }
 // traversal-stack entries a lane keeps in LDS (deeper ones: global overflow column)
 __host__ __device__ constexpr uint32_t lds_stack_entries(int t) {
     return t == TIER_BASIC ? RT_STACK_BASIC : t == TIER_MESH ? RT_STACK_MESH : tier_full_bvh(t) ? RT_STACK_FULL : RT_STACK_FLAT;
@@ -160,6 +164,15 @@ extern "C" __attribute__((weak)) hipError_t rtk_launch_hits(const rtk::SceneView
 extern "C" __attribute__((weak)) hipError_t rtk_launch_occluded(const rtk::SceneView* view, const struct rt_ray* rays,
                                                                 uint8_t* out, uint64_t n, uint64_t seed, int tier,
                                                                 int grid, void* stack_ovf, hipStream_t stream);
+// The Disney self-test (rt_disney_selftest): fn's doubles per case in and out
+// (0 for an unknown fn), and n cases of the BSDF's device functions as the
+// path kernel's Disney tier compiles them.  Weak as rtk_launch_hits is: absent
+// from the launcher's CPU test build, where the call reports RT_EUNSUPPORTED.
+struct rt_disney_params;
+extern "C" __attribute__((weak)) int rtk_disney_widths(int fn, int* in_w, int* out_w);
+extern "C" __attribute__((weak)) hipError_t rtk_launch_disney(int fn, const struct rt_disney_params* params,
+                                                              const double* base_color, const double* in, double* out,
+                                                              uint64_t n, hipStream_t stream);
 // device bytes rtk_launch_frame needs at params_dev
 extern "C" size_t rtk_params_bytes(void);
 extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu);

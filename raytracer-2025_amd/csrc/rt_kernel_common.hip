@@ -147,6 +147,7 @@ __global__ void __launch_bounds__(256) rt_math_kernel(int fn, int impl, const do
             case 6: r = rtcr::atan2(x, y); break;
             case 8: rtcr::sincos_2pi(x, &s, &c), r = s; break;
             case 9: rtcr::sincos_2pi(x, &s, &c), r = c; break;
+            case 10: r = rtcr::pow_2m4(x); break;
             default: r = k_sqrt(x); break;  // the path's square root (RT_FAST_SQRT)
         }
     } else {
@@ -160,6 +161,7 @@ __global__ void __launch_bounds__(256) rt_math_kernel(int fn, int impl, const do
             case 6: r = ::atan2(x, y); break;
             case 8: ::sincos(2.0 * PI * x, &s, &c), r = s; break;
             case 9: ::sincos(2.0 * PI * x, &s, &c), r = c; break;
+            case 10: r = ::pow(0.0625, x); break;
             default: r = ::sqrt(x); break;
         }
     }
@@ -368,7 +370,8 @@ extern "C" hipError_t rtk_launch_frame(const rtk::SceneView* view, const rtk_fra
         : tier == rtk::TIER_MESH ? rtk_launch_path_1(grid, stream, Pd)
         : tier == rtk::TIER_FULL ? rtk_launch_path_2(grid, stream, Pd)
         : tier == rtk::TIER_FULL_FLAT ? rtk_launch_path_3(grid, stream, Pd)
-                                      : rtk_launch_path_4(grid, stream, Pd);
+        : tier == rtk::TIER_FULL_GL ? rtk_launch_path_4(grid, stream, Pd)
+                                    : rtk_launch_path_5(grid, stream, Pd);
     if (e != hipSuccess) return e;
     if (fd->ev_stop) (void)hipEventRecord((hipEvent_t)fd->ev_stop, stream);
     return launch_reduce(fd, K.F, partial, out, srgb, toon, stream);
@@ -451,5 +454,6 @@ extern "C" int rtk_path_kernel_occupancy(int tier, int* blocks_per_cu) {
          : tier == rtk::TIER_MESH ? rtk_occupancy_1(blocks_per_cu)
          : tier == rtk::TIER_FULL ? rtk_occupancy_2(blocks_per_cu)
          : tier == rtk::TIER_FULL_FLAT ? rtk_occupancy_3(blocks_per_cu)
-                                       : rtk_occupancy_4(blocks_per_cu);
+         : tier == rtk::TIER_FULL_GL ? rtk_occupancy_4(blocks_per_cu)
+                                     : rtk_occupancy_5(blocks_per_cu);
 }

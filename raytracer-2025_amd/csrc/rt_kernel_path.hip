@@ -2,7 +2,7 @@
 // points of its tiers.  The product library compiles this unit once per tier
 // (-DRT_TIER=N, each object with its own code-generation flags:
 // raytracer-2025_amd/Makefile); with RT_TIER undefined it instantiates all
-// five tiers and the basic tier's wide variant (the whole build,
+// six tiers and the basic tier's wide variant (the whole build,
 // rt_kernel.hip).  The trace, check and diag builds' readers live here, with
 // the kernels that write what they read.
 #include <hip/hip_runtime.h>
@@ -718,6 +718,79 @@ RT_TIER_ENTRY(3)
 #endif
 #if !defined(RT_TIER) || RT_TIER == 4
 RT_TIER_ENTRY(4)
+#endif
+#if !defined(RT_TIER) || RT_TIER == 5
+RT_TIER_ENTRY(5)
+
+// Disney self-test (rt_disney_selftest): the device functions shade<TIER_FULL_DS>
+// calls, in this tier's object and so under its flags, one case per thread.
+//  fn 0  Disney::evaluate_disney: local v_out[3], local v_in[3], front_face
+//        -> reflectance[3], forward pdf, reverse pdf, panic
+//  fn 1  Disney::scatter's v_out + DisneyPDF::new + generate, the draws given:
+//        world normal[3], world -r_in.direction[3], front_face, four unit draws
+//        in call order -> 1 / 0 (Some / None), direction[3], draws consumed, panic
+// A case that panics writes zeros and the flag.
+namespace rtk {
+__global__ void __launch_bounds__(256) rt_disney_kernel(int fn, DDisney R, D3 base_color, int in_w, int out_w,
+                                                       const double* __restrict__ in, double* __restrict__ out,
+                                                       uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* p = in + i * (uint64_t)in_w;
+    double* q = out + i * (uint64_t)out_w;
+    disney::Params P;
+    P.base_color = base_color;
+    P.roughness = R.roughness, P.anisotropic = R.anisotropic, P.sheen = R.sheen, P.sheen_tint = R.sheen_tint;
+    P.clearcoat = R.clearcoat, P.clearcoat_gloss = R.clearcoat_gloss, P.specular_tint = R.specular_tint;
+    P.metallic = R.metallic, P.ior = R.ior, P.flatness = R.flatness, P.spec_trans = R.spec_trans;
+    P.diff_trans = R.diff_trans;
+    P.thin = R.thin != 0;
+    bool panic = false;
+    double r[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (fn == 0) {
+        D3 f;
+        double fwd, rev;
+        disney::evaluate_disney(P, d3(p[0], p[1], p[2]), d3(p[3], p[4], p[5]), p[6] != 0.0, f, fwd, rev, panic);
+        r[0] = f.x, r[1] = f.y, r[2] = f.z, r[3] = fwd, r[4] = rev;
+    } else {
+        const disney::Pdf pdf = disney::pdf_new(d3(p[0], p[1], p[2]), d3(p[3], p[4], p[5]), p[6] != 0.0, panic);
+        if (!panic) {
+            const double u[4] = {p[7], p[8], p[9], p[10]};
+            disney::ArrayDraw dr{u, 0};
+            D3 dir = d3(0.0, 0.0, 0.0);
+            const bool some = disney::generate_impl(P, pdf, dr, dir, panic);
+            r[0] = some ? 1.0 : 0.0;
+            if (some) r[1] = dir.x, r[2] = dir.y, r[3] = dir.z;
+            r[4] = (double)dr.n;
+        }
+    }
+    for (int k = 0; k < 5; ++k) q[k] = panic ? 0.0 : r[k];
+    q[5] = panic ? 1.0 : 0.0;
+}
+}  // namespace rtk
+
+extern "C" int rtk_disney_widths(int fn, int* in_w, int* out_w) {
+    if (fn < 0 || fn > 1) return 0;
+    *in_w = fn == 0 ? 7 : 11;
+    *out_w = 6;
+    return 1;
+}
+
+extern "C" hipError_t rtk_launch_disney(int fn, const rt_disney_params* params, const double* base_color,
+                                        const double* in, double* out, uint64_t n, hipStream_t stream) {
+    int in_w = 0, out_w = 0;
+    if (!rtk_disney_widths(fn, &in_w, &out_w)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    rtk::DDisney R{};
+    R.roughness = params->roughness, R.anisotropic = params->anisotropic, R.sheen = params->sheen;
+    R.sheen_tint = params->sheen_tint, R.clearcoat = params->clearcoat, R.clearcoat_gloss = params->clearcoat_gloss;
+    R.specular_tint = params->specular_tint, R.metallic = params->metallic, R.ior = params->ior;
+    R.flatness = params->flatness, R.spec_trans = params->spec_trans, R.diff_trans = params->diff_trans;
+    R.thin = params->thin != 0;
+    hipLaunchKernelGGL(rtk::rt_disney_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fn, R,
+                       rtk::D3{base_color[0], base_color[1], base_color[2]}, in_w, out_w, in, out, n);
+    return hipGetLastError();
+}
 #endif
 #if defined(RT_WAVE_TRACE)
 extern "C" int rt_lane_trace(unsigned long long* out, uint64_t n_lanes) {

@@ -165,13 +165,14 @@ enum MatType : int32_t {
     M_EMPTY = 5,
     M_TRANSPARENT = 6,
     M_MIX = 7,
+    M_DISNEY = 8,
 };
 
 // material.rs: one record per Arc<dyn Material>
 struct alignas(16) DMaterial {
     int32_t type;
     int32_t tex;       // albedo / attenuation / emission texture
-    int32_t inner;     // DiffuseLight inner material, Mix mat1
+    int32_t inner;     // DiffuseLight inner material, Mix mat1; Disney: its DDisney record
     int32_t inner2;    // Mix mat2
     double albedo[3];  // Metal albedo; the solid texture's colour (MF_SOLID)
     double fuzz;       // Metal fuzz (clamped), Dielectric ior, Mix ratio
@@ -180,6 +181,17 @@ struct alignas(16) DMaterial {
 };
 // MF_SOLID: tex is a SolidColor, whose colour albedo holds (not for Metal)
 enum : uint32_t { MF_NEEDS_UV = 1u, MF_EMISSIVE = 2u, MF_SOLID = 4u };
+
+// DisneyParameters (material/disney.rs:17-34) without base_color, which is the
+// material's texture at the hit (Disney::param_fn): the record DMaterial::inner
+// of an M_DISNEY material indexes
+struct alignas(16) DDisney {
+    double roughness, anisotropic, sheen, sheen_tint, clearcoat, clearcoat_gloss, specular_tint, metallic, ior, flatness,
+        spec_trans, diff_trans;
+    int32_t thin;
+    int32_t pad[3];
+};
+static_assert(sizeof(DDisney) == 112, "DDisney must be 112 B (7 dwordx4)");
 
 enum TexType : int32_t {
     T_SOLID = 0,
@@ -217,7 +229,11 @@ struct SceneView {
     const RT_GLOBAL double4* msph_dir;       // {c2-c1, 0}
     const RT_GLOBAL int32_t* msph_mat;
     const RT_GLOBAL DPlanar* planars;        // quads then triangles share the record
-    const RT_GLOBAL PlanarF* planars_f;      // unused (rt_planar_filter.h: no kernel runs the pre-test): null
+    // Disney parameter records (DMaterial::inner of M_DISNEY).  In the slot of
+    // the planar pre-test's table, which no kernel read (rt_planar_filter.h),
+    // not appended: a longer SceneView moves the Frame behind it in the launch
+    // parameters, and tier 4 then compiles to 16 B/lane more scratch
+    const RT_GLOBAL DDisney* disney;
     const RT_GLOBAL double* planar_area;
     const RT_GLOBAL int32_t* planar_mat;
     const RT_GLOBAL int32_t* planar_remap;   // index into remaps, -1 = plain Triangle/Quad
@@ -265,6 +281,7 @@ enum : uint32_t {
     F_GENERAL = 512u,  // tier FULL_GL: lights beyond a flat list of static primitives, nested
                        // DiffuseLight / Mix wrappers, Mix::from_image ratios
     F_NORMALMAP = 256u,  // ... with a normal map (full tier: image textures)
+    F_DISNEY = 1024u,    // tier FULL_DS: a Disney material (rt_disney.h)
 };
 
 }  // namespace rtk

@@ -15,8 +15,10 @@ extern "C" hipError_t rtk_launch_path_1(int, hipStream_t, const rtk::KParams*);
 extern "C" hipError_t rtk_launch_path_2(int, hipStream_t, const rtk::KParams*);
 extern "C" hipError_t rtk_launch_path_3(int, hipStream_t, const rtk::KParams*);
 extern "C" hipError_t rtk_launch_path_4(int, hipStream_t, const rtk::KParams*);
+extern "C" hipError_t rtk_launch_path_5(int, hipStream_t, const rtk::KParams*);
 extern "C" int rtk_occupancy_0(int*);
 extern "C" int rtk_occupancy_1(int*);
 extern "C" int rtk_occupancy_2(int*);
 extern "C" int rtk_occupancy_3(int*);
 extern "C" int rtk_occupancy_4(int*);
+extern "C" int rtk_occupancy_5(int*);

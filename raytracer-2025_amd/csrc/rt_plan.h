@@ -20,6 +20,7 @@ namespace plan {
 // stack and node copy the launcher checks itself (rt_render.cpp prepare_tier).
 inline int tier_for(uint32_t features) {
     const uint32_t full = F_XFORM | F_MEDIUM | F_MSPHERE | F_LIGHTS | F_TEXFULL | F_MATFULL | F_NORMALMAP;
+    if (features & F_DISNEY) return 5;           // TIER_FULL_DS
     if (features & F_GENERAL) return 4;          // TIER_FULL_GL
     if (features & full) return 2;               // TIER_FULL
     if (features & (F_PLANAR | F_REMAP)) return 1;  // TIER_MESH

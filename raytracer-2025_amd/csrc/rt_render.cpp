@@ -127,6 +127,10 @@ struct DeviceWorld {
     int32_t world = -1, lights = -1, background = -1;
     uint64_t generation = ~0ull;
     bool reference_bvh = false;
+    // a Disney world flattened for rt_world_hit / rt_world_occluded: laid out
+    // for the tier it takes without F_DISNEY (build_flat), so not a render's
+    bool query_flat = false;
+    bool has_disney = false;  // the world as flattened holds a Disney material
     char* blob = nullptr;
     size_t blob_bytes = 0;
     rtk::SceneView view{};
@@ -330,7 +334,6 @@ static void pack_world(const HostWorld& hw, std::vector<char>& blob, rtk::SceneV
     v.msph_dir = (const double4*)off(put(blob, hw.msph_dir));
     v.msph_mat = (const int32_t*)off(put(blob, hw.msph_mat));
     v.planars = (const rtk::DPlanar*)off(put(blob, hw.planars));
-    v.planars_f = nullptr;  // (no kernel reads it)
     v.planar_area = (const double*)off(put(blob, hw.planar_area));
     v.planar_mat = (const int32_t*)off(put(blob, hw.planar_mat));
     v.planar_remap = (const int32_t*)off(put(blob, hw.planar_remap));
@@ -345,6 +348,7 @@ static void pack_world(const HostWorld& hw, std::vector<char>& blob, rtk::SceneV
     v.textures = (const rtk::DTexture*)off(put(blob, hw.textures));
     v.texels = (const float*)off(put(blob, hw.texels));
     v.perlin = (const rtk::DPerlin*)off(put(blob, hw.perlin));
+    v.disney = (const rtk::DDisney*)off(put(blob, hw.disney));
     // the mesh tier reads 128 B from any record's address (rt_walk.h
     // unified_load): slack past the last array
     blob.resize(((blob.size() + 255) & ~(size_t)255) + 256, 0);
@@ -363,6 +367,11 @@ struct FlatWorld {
     std::vector<char> blob;
     rtk::SceneView rel{};  // SceneView with byte offsets into blob instead of pointers
     size_t n_prims = 0;
+    // for_query: the world of a hit / occlusion query.  Materials do not reach
+    // those kernels, so a Disney world takes the tier, and with it the node
+    // format, it would take without F_DISNEY
+    bool for_query = false;
+    bool has_disney = false;
 };
 
 static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg, bool reference_bvh, FlatWorld& fw) {
@@ -375,6 +384,8 @@ static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg
     auto t0 = std::chrono::steady_clock::now();
     HostWorld hw;
     int32_t rc = flatten(s, world, lights, bg, reference_bvh, hw);
+    fw.has_disney = rc == RT_OK && (hw.features & rtk::F_DISNEY) != 0;
+    if (fw.for_query) hw.features &= ~rtk::F_DISNEY;
     int tier = rc == RT_OK ? prepare_tier(hw) : -1;
     if (rc == RT_OK && tier < 0) rc = RT_ESTACK;
 #ifdef RT_CHECK
@@ -484,7 +495,7 @@ static int32_t upload_world(rt_scene* s, DeviceWorld* d, int32_t world, int32_t 
                             FlatWorld& fw, double& flatten_ms) {
     flatten_ms = 0;
     if (d->blob && d->world == world && d->lights == lights && d->background == bg && d->generation == s->generation &&
-        d->reference_bvh == reference_bvh)
+        d->reference_bvh == reference_bvh && (fw.for_query ? (d->query_flat || !d->has_disney) : !d->query_flat))
         return RT_OK;
     auto t0 = std::chrono::steady_clock::now();
     int32_t rc = build_flat(s, world, lights, bg, reference_bvh, fw);
@@ -516,9 +527,11 @@ static int32_t upload_world(rt_scene* s, DeviceWorld* d, int32_t world, int32_t 
     fix(v.nodes), fix(v.nodes4), fix(v.spheres), fix(v.sphere_mat), fix(v.sphere_rinv), fix(v.msph_center), fix(v.msph_dir),
         fix(v.msph_mat), fix(v.planars), fix(v.planar_area), fix(v.planar_mat), fix(v.planar_remap), fix(v.remaps),
         fix(v.remap_nm), fix(v.list_children), fix(v.list_boxes), fix(v.xforms), fix(v.media), fix(v.materials), fix(v.textures),
-        fix(v.texels), fix(v.perlin);
+        fix(v.texels), fix(v.perlin), fix(v.disney);
     d->view = v;
     d->tier = fw.tier;
+    d->has_disney = fw.has_disney;
+    d->query_flat = fw.for_query && fw.has_disney;
     d->reference_bvh = reference_bvh;
     d->blob_bytes = fw.blob.size();
     d->world = world;
@@ -1103,6 +1116,7 @@ static int32_t hit_enqueue(rt_scene* s, int32_t world, uint64_t seed, uint32_t f
     int32_t rc = slot_for(r, 0, cur, d);
     if (rc != RT_OK) return rc;
     FlatWorld fw;
+    fw.for_query = true;
     double flatten_ms = 0;
     if ((rc = upload_world(s, d, world, -1, -1, (flags & RT_FLAG_REFERENCE_BVH) != 0, fw, flatten_ms)) != RT_OK)
         return rc;
@@ -1287,7 +1301,7 @@ int32_t rt_to_rgb_device(const float* lin_dev, uint8_t* srgb_dev, uint64_t n_val
 }
 
 int32_t rt_math_selftest(int32_t fn, int32_t impl, const double* a, const double* b, double* out, uint64_t n) {
-    if (fn < 0 || fn > 9 || impl < 0 || impl > 1) return set_error(RT_EINVAL, "unknown function or implementation");
+    if (fn < 0 || fn > 10 || impl < 0 || impl > 1) return set_error(RT_EINVAL, "unknown function or implementation");
     if (n && (!a || !out || (fn == 6 && !b))) return set_error(RT_EINVAL, "null argument");
     if (n == 0) return RT_OK;
     int dev = 0;
@@ -1331,6 +1345,35 @@ int32_t rt_walk_selftest(int32_t fn, const double* in, double* out, uint64_t n) 
         (e = rtk_launch_walk(fn, d, d_out, n, nullptr)) != hipSuccess ||
         (e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
         rc = hip_fail(e, "walk self-test");
+    (void)hipFree(d);
+    return rc;
+}
+
+int32_t rt_disney_selftest(int32_t fn, const rt_disney_params* params, const double base_color[3], const double* in,
+                           double* out, uint64_t n) {
+    if (!rtk_launch_disney || !rtk_disney_widths)
+        return set_error(RT_EUNSUPPORTED, "this build holds no Disney self-test kernel");
+    int in_w = 0, out_w = 0;
+    if (!rtk_disney_widths(fn, &in_w, &out_w)) return set_error(RT_EINVAL, "unknown function");
+    if (!params || !base_color || (n && (!in || !out))) return set_error(RT_EINVAL, "null argument");
+    if (params->struct_size < sizeof(rt_disney_params)) return set_error(RT_EINVAL, "rt_disney_params.struct_size too small");
+    if (n == 0) return RT_OK;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return set_error(RT_EDEVICE, std::string("librt_mi355x.so needs a gfx950 device, found ") + prop.gcnArchName);
+    double* d = nullptr;
+    const size_t in_bytes = n * in_w * sizeof(double), out_bytes = n * out_w * sizeof(double);
+    if ((e = hipMalloc(&d, in_bytes + out_bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    double* d_out = d + n * in_w;
+    int32_t rc = RT_OK;
+    if ((e = hipMemcpy(d, in, in_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = rtk_launch_disney(fn, params, base_color, d, d_out, n, nullptr)) != hipSuccess ||
+        (e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = hip_fail(e, "Disney self-test");
     (void)hipFree(d);
     return rc;
 }

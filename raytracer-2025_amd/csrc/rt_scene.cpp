@@ -948,12 +948,13 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
         rtk::DMaterial m{};
         m.type = r.type;
         m.tex = r.tex;
-        m.inner = r.inner;
+        m.inner = r.type == rtk::M_DISNEY ? r.disney : r.inner;
         m.inner2 = r.inner2;
         for (int k = 0; k < 3; ++k) m.albedo[k] = r.albedo[k];
         m.fuzz = r.param;
         out.materials.push_back(m);
     }
+    out.disney = s->disneys;
     // flags: uv need and emission, resolved through DiffuseLight/Mix nesting
     for (size_t i = 0; i < out.materials.size(); ++i) {
         rtk::DMaterial& m = out.materials[i];
@@ -1015,6 +1016,7 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
     while (!work.empty()) {
         const int m = work.back();
         work.pop_back();
+        if (out.materials[m].type == rtk::M_DISNEY) continue;  // (its inner is a DDisney record)
         use_mat(out.materials[m].inner);
         use_mat(out.materials[m].inner2);
     }
@@ -1046,6 +1048,7 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
         if (m.type == rtk::M_DIFFUSE_LIGHT || m.type == rtk::M_ISOTROPIC || m.type == rtk::M_TRANSPARENT ||
             m.type == rtk::M_MIX)
             out.features |= rtk::F_MATFULL;
+        if (m.type == rtk::M_DISNEY) out.features |= rtk::F_DISNEY;
     }
     // Wrapper materials (DiffuseLight with a material, Mix): the C3 / C5 tiers
     // take one level whose Mix ratio is a constant; deeper trees and
@@ -1307,6 +1310,33 @@ int32_t rt_mat_mix(rt_scene* s, int32_t m1, int32_t m2, double ratio) {
     m.inner = m1;
     m.inner2 = m2;
     m.param = ratio;
+    return push_mat(s, m);
+}
+
+void rt_disney_params_default(rt_disney_params* p) {  // disney.rs:36-55
+    if (!p) return;
+    *p = rt_disney_params{};
+    p->struct_size = (uint32_t)sizeof(rt_disney_params);
+    p->roughness = 0.5;
+    p->ior = 1.45;
+}
+int32_t rt_mat_disney(rt_scene* s, int32_t tex, const rt_disney_params* p) {
+    if (!s || !p) return set_error(RT_EINVAL, "null argument");
+    if (p->struct_size < sizeof(rt_disney_params)) return set_error(RT_EINVAL, "rt_disney_params.struct_size too small");
+    rtk::DDisney d{};
+    d.roughness = p->roughness, d.anisotropic = p->anisotropic, d.sheen = p->sheen, d.sheen_tint = p->sheen_tint;
+    d.clearcoat = p->clearcoat, d.clearcoat_gloss = p->clearcoat_gloss, d.specular_tint = p->specular_tint;
+    d.metallic = p->metallic, d.ior = p->ior, d.flatness = p->flatness, d.spec_trans = p->spec_trans;
+    d.diff_trans = p->diff_trans;
+    d.thin = p->thin != 0;
+    for (const double* f = &d.roughness; f <= &d.diff_trans; ++f)
+        if (!std::isfinite(*f)) return set_error(RT_EINVAL, "non-finite Disney parameter");
+    if (!tex_ok(s, tex)) return set_error(RT_EHANDLE, "unknown texture");
+    s->disneys.push_back(d);
+    MatRec m{};
+    m.type = rtk::M_DISNEY;
+    m.tex = tex;
+    m.disney = (int)s->disneys.size() - 1;
     return push_mat(s, m);
 }
 

@@ -103,6 +103,7 @@ struct MatRec {
     int tex = -1, inner = -1, inner2 = -1;
     double albedo[3] = {0, 0, 0};
     double param = 0;
+    int disney = -1;  // M_DISNEY: index into rt_scene::disneys
 };
 
 // Flattened world on the host, ready to upload as one blob.
@@ -128,6 +129,7 @@ struct HostWorld {
     std::vector<rtk::DTexture> textures;
     std::vector<float> texels;
     std::vector<rtk::DPerlin> perlin;
+    std::vector<rtk::DDisney> disney;  // the records DMaterial::inner of an M_DISNEY material indexes
     uint32_t world_root = 0, lights_root = 0;
     uint32_t stack_need = 0;
     uint32_t features = 0;
@@ -145,6 +147,7 @@ struct rt_scene {
     std::vector<rth::MatRec> mats;
     std::vector<float> texels;
     std::vector<rtk::DPerlin> perlins;
+    std::vector<rtk::DDisney> disneys;
     uint32_t next_medium_id = 0;
     uint64_t generation = 0;  // bumped by every mutation; invalidates the device cache
     // device-side cache and the last render's state (rt_render.cpp)

@@ -2,6 +2,7 @@
 // scatter, the PDF mix (shade), and the basic tier's merged form of a hit
 // (shade_hit_basic).
 #pragma once
+#include "rt_disney.h"
 #include "rt_geom.h"
 #include "rt_kernel.h"
 #include "rt_lights.h"
@@ -136,7 +137,7 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
     // into cos/sin(2 pi r1) (vec3.rs:313-322, 333-343): the main loop's Draws.
     constexpr bool HOIST = !FULL;
     const double xi0 = Dr.xi0, xi1 = Dr.xi1, sn0 = Dr.sn, cs0 = Dr.cs;
-    if constexpr (TIER == TIER_FULL_GL) {
+    if constexpr (tier_general(TIER)) {
         if (M.flags & MF_EMISSIVE) L = L + beta * emitted_tree<RT_MAT_DEPTH>(S, rec.mat, rec.u, rec.v, rec.p);
         // the wrappers' scatter: DiffuseLight -> its material or None, Mix -> one draw (material.rs:180-185, 254-260)
         for (int k = 0; k < RT_MAT_DEPTH && (M.type == M_DIFFUSE_LIGHT || M.type == M_MIX); ++k) {
@@ -174,8 +175,10 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
         }
     }
     const D3 n = rec.n;
-    int pdf_kind = -1;  // 0 cosine, 1 sphere
+    int pdf_kind = -1;  // 0 cosine, 1 sphere, 2 Disney (TIER_FULL_DS)
     D3 albedo = d3(0, 0, 0);
+    disney::Params dsp{};  // (TIER_FULL_DS only: unused, so absent, elsewhere)
+    disney::Pdf dsq{};
     switch (M.type) {
         case M_LAMBERTIAN:  // material.rs:60-65
             albedo = mat_tex<FULL, PL>(S, M, rec.u, rec.v, rec.p);
@@ -231,6 +234,15 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
             break;
         }
         default:
+            if constexpr (TIER == TIER_FULL_DS) {
+                if (M.type == M_DISNEY) {  // Disney::scatter (disney.rs:71-89): param_fn at the hit, DisneyPDF::new
+                    dsp = disney::make_params(S.disney[M.inner], mat_tex<FULL, PL>(S, M, rec.u, rec.v, rec.p));
+                    dsq = disney::pdf_new(n, -ray.d, rec.front, panic);
+                    if (panic) return true;
+                    pdf_kind = 2;
+                    break;
+                }
+            }
             if constexpr (FULL) {
                 if (M.type == M_ISOTROPIC) {  // material.rs:199-206
                     albedo = mat_tex<FULL, PL>(S, M, rec.u, rec.v, rec.p);
@@ -252,7 +264,15 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
         D3 dir;
         bool ok = true;
         if (from_material) {
-            if (!FULL || pdf_kind == 0) {  // CosinePDF::generate (pdf.rs:59-63), vec3.rs:333-343
+            if (TIER == TIER_FULL_DS && pdf_kind == 2) {
+                // DisneyPDF::generate; None ends the path with the emission only (camera.rs:313-315)
+                if constexpr (TIER == TIER_FULL_DS) {
+                    if (!disney::generate(dsp, dsq, rng, ovf, dir, panic)) {
+                        if (ovf) panic = true;
+                        return true;
+                    }
+                }
+            } else if (!FULL || pdf_kind == 0) {  // CosinePDF::generate (pdf.rs:59-63), vec3.rs:333-343
                 double r2 = xi1, sn = sn0, cs = cs0;
                 if constexpr (!HOIST) {
                     const double r1 = rng.next(ovf);
@@ -265,7 +285,7 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
                 dir = random_unit_vector(rng, ovf);
             }
         } else {
-            if constexpr (TIER == TIER_FULL_GL)
+            if constexpr (tier_general(TIER))
                 dir = light_random_tree<RT_LIGHT_DEPTH>(S, S.lights_root, rec.p, rng, ovf, ok);
             else
                 dir = light_random(S, rec.p, rng, ovf, ok);
@@ -274,7 +294,9 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
         // value (pdf.rs:22-28, 50-57, 101-111)
         D3 f;
         double pdf;
-        if (!FULL || pdf_kind == 0) {
+        if (TIER == TIER_FULL_DS && pdf_kind == 2) {  // DisneyPDF::value (disney.rs:662-670)
+            if constexpr (TIER == TIER_FULL_DS) disney::pdf_value(dsp, dsq, dir, f, pdf, panic);
+        } else if (!FULL || pdf_kind == 0) {
             bool okd;
             const D3 ud = unit(dir, okd);
             if (!okd) panic = true;
@@ -288,7 +310,7 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
         }
         if (use_lights) {
             double pdf1;
-            if constexpr (TIER == TIER_FULL_GL)
+            if constexpr (tier_general(TIER))
                 pdf1 = light_pdf_tree<RT_LIGHT_DEPTH>(S, S.lights_root, rec.p, dir, panic);
             else
                 pdf1 = light_pdf(S, rec.p, dir);

@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from .capi import Api, RtCamera, RtError, RtHitRecord, RtRay, RtRenderOpts, RtStats, d3, d4
+from .capi import Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtRay, RtRenderOpts, RtStats, d3, d4
 
 # rt_hit_record as a numpy record (80 B, the C layout)
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
@@ -153,6 +153,24 @@ class Scene:
     def Mix_from_image(self, mat1, mat2, image_tex):
         """Mix::from_image (material.rs:235-247): ratio = the texture's alpha."""
         return Material(self, self._c(self.api.mat_mix_image(self.s, mat1.h, mat2.h, image_tex.h)))
+
+    def disney_params(self, **params):
+        """rt_disney_params: DisneyParameters::default (disney.rs:36-55) with the given fields set."""
+        p = RtDisneyParams()
+        self.api.disney_params_default(C.byref(p))
+        for name, value in params.items():
+            if name in ("struct_size",) or not hasattr(p, name):
+                raise TypeError(f"unknown Disney parameter {name!r}")
+            setattr(p, name, int(bool(value)) if name == "thin" else float(value))
+        return p
+
+    def Disney(self, tex, **params):
+        """Disney::builder()...build() with base_color from `tex` at the hit
+        (material/disney.rs:59-61, obj.rs:279-292); `params`: roughness,
+        anisotropic, sheen, sheen_tint, clearcoat, clearcoat_gloss,
+        specular_tint, metallic, ior, flatness, spec_trans, diff_trans, thin."""
+        p = self.disney_params(**params)
+        return Material(self, self._c(self.api.mat_disney(self.s, tex.h, C.byref(p))))
 
     # ---- hittables
     def Sphere(self, center, radius, mat):
