@@ -373,6 +373,15 @@ int32_t rt_render_gather_mode(const rt_scene* s);
  * rows * W * sqrt_spp * 3.  Waits for the render. */
 int32_t rt_render_partials_get(rt_scene* s, double* out, uint64_t n_values);
 
+/* Test hook (parity tooling, not part of the reference surface): the
+ * primary-ray candidate table of the last single-device render on this scene,
+ * 8 sphere indices per pixel laid out [rows x W][8] -- ascending, 0xfffe in
+ * the unused slots, 0xffff in slot 0 of a pixel whose primary rays walk the
+ * tree.  n_values must equal rows * W * 8.  RT_EUNSUPPORTED when the render's
+ * kernel builds no table (every tier but the basic one, and its wide
+ * variant).  Waits for the render. */
+int32_t rt_render_primary_get(rt_scene* s, uint16_t* out, uint64_t n_values);
+
 /* Test hook (parity tooling, not part of the reference surface): n calls of
  * one f64 function on the current gfx950 device, from host arrays a (and b)
  * into out.  fn: 0 sin, 1 cos, 2 sincos's sin, 3 sincos's cos, 4 log (ln),

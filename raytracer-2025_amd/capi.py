@@ -168,6 +168,7 @@ SIGNATURES = {
     "camera_from_json": (_I, [C.c_char_p, C.POINTER(RtCamera)]),
     "world_info_get": (_I, [_P, _I, _I, _I, _U, C.POINTER(RtWorldInfo)]),
     "render_partials_get": (_I, [_P, _DP, C.c_uint64]),
+    "render_primary_get": (_I, [_P, C.POINTER(C.c_uint16), C.c_uint64]),
     "math_selftest": (_I, [_I, _I, _DP, _DP, _DP, C.c_uint64]),
     "walk_selftest": (_I, [_I, _DP, _DP, C.c_uint64]),
     "disney_selftest": (_I, [_I, C.POINTER(RtDisneyParams), _DP, _DP, _DP, C.c_uint64]),
@@ -180,7 +181,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

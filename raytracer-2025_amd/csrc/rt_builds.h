@@ -39,10 +39,14 @@ struct Diag {
     // ... per shading class (the 11 above): rounds in which it is present,
     // and its lanes
     unsigned long long cls_rounds[11] = {}, cls_lanes[11] = {};
+    // basic tier, batch variant: the wave cycles of the camera stage (camera
+    // draws, camera ray, candidate tests), the primary rays resolved from
+    // the candidate table and the exact tests they ran
+    unsigned long long cyc_camera = 0, prim_rays = 0, prim_tests = 0;
 #endif
 };
 #ifdef RT_DIAG
-constexpr int RT_DIAG_N = 61;
+constexpr int RT_DIAG_N = 64;
 __device__ unsigned long long g_diag[RT_DIAG_N];
 #define RT_DIAG_ONLY(x) x
 #else
@@ -102,6 +106,12 @@ struct RayHist {
 // array.
 constexpr uint32_t K_CHECK_SLAB = 15;
 static_assert(K_CHECK_SLAB > K_POPXF, "the slab guard's marker must not be a ref kind");
+// The basic tier's primary-ray guard (rt_kernel_path.hip: a camera ray resolved
+// from its pixel's candidates is also walked) likewise: "kind 14, index
+// <pixel>" is a pixel whose walk found another hit, or another t, than the
+// candidate tests.
+constexpr uint32_t K_CHECK_PRIMARY = 14;
+static_assert(K_CHECK_PRIMARY > K_POPXF, "the primary-ray guard's marker must not be a ref kind");
 __device__ unsigned long long g_check[2];
 __device__ __noinline__ void check_fail(uint32_t ref) {
     atomicAdd(&g_check[0], 1ull);

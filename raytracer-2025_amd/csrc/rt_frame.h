@@ -57,6 +57,13 @@ struct KParams {
     double* partial;  // [queue_total][3]: the f64 sum of each queue entry's samples
     unsigned long long* stats;
     RT_GLOBAL uint2* stack_ovf;  // mesh / full tiers: [stack_need - LDS entries][grid * RT_BLOCK]
+    // Basic tier, batch variant: the launch's primary-ray candidates
+    // (rt_primary.h: PRIMARY_CAP sphere indices per launch pixel, filled by
+    // rt_primary_kernel ahead of the path kernel), and 1 / row_stride rounded
+    // up (udiv_inv: image row -> shard row).  Appended, so that every other
+    // field keeps its offset and the other kernels their code.
+    const RT_GLOBAL uint4* cand;
+    double inv_stride;
 };
 
 }  // namespace rtk

@@ -103,6 +103,10 @@ struct rtk_frame_desc {
     double center[3], pixel00[3], du[3], dv[3], disk_u[3], disk_v[3];
     void* ev_start;  // hipEvent_t recorded around the path kernel (or NULL)
     void* ev_stop;
+    // the launch's primary-ray candidate table (rt_primary.h: primary_table_bytes
+    // of device memory), or NULL: given for the basic tier's batch variant,
+    // whose launch fills it ahead of the path kernel, inside the timed span
+    void* primary;
 };
 
 extern "C" int rtk_tier_for(uint32_t features);

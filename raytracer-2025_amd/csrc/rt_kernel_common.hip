@@ -9,6 +9,7 @@
 #include "rt_math.h"
 #include "rt_slab.h"
 #include "rt_sphere_filter.h"
+#include "rt_primary.h"
 #include "rt_plan.h"
 #include "rt_queue.h"
 #include "rt_frame.h"
@@ -223,6 +224,69 @@ __global__ void __launch_bounds__(256) rt_walk_kernel(int fn, int in_w, int out_
     }
 }
 
+// The primary-ray candidate table of one launch (rt_primary.h): for every
+// launch pixel the spheres a camera ray of that pixel may hit, by the
+// conservative beam test.  One 256-thread block per tile of 16 x 16 launch
+// pixels: the block first tests every sphere against the tile's beam (the
+// footprint of all its pixels) into a bit set in LDS, then each thread tests
+// the tile's spheres against its own pixel's beam, in index order, and stores
+// the pixel's eight slots as one 16-byte word.  K.cand of the launch
+// parameters is the table: rows * W uint4, which the grid's tiles cover --
+// a thread whose pixel lies outside the launch's W x rows stores nothing.
+__global__ void __launch_bounds__(PRIMARY_TILE * PRIMARY_TILE) rt_primary_kernel(const KParams* __restrict__ P) {
+    const SceneView& S = P->S;
+    const Frame& F = P->F;
+    constexpr uint32_t BLK = PRIMARY_TILE * PRIMARY_TILE;
+    __shared__ uint32_t bits[PRIMARY_MAX_SPHERES / 32u];
+    const uint32_t n = min(S.n_ref[K_SPHERE], PRIMARY_MAX_SPHERES), words = (n + 31u) / 32u;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < words; k += BLK) bits[k] = 0u;
+    __syncthreads();
+    BeamCam C;
+    auto cp3 = [](double* dst, const D3& v) { dst[0] = v.x, dst[1] = v.y, dst[2] = v.z; };
+    cp3(C.center, F.center), cp3(C.disk_u, F.disk_u), cp3(C.disk_v, F.disk_v);
+    cp3(C.pixel00, F.pixel00), cp3(C.du, F.du), cp3(C.dv, F.dv);
+    C.defocus = F.defocus;
+    // the tile: launch pixels [x0, x1) x shard rows [r0, r1) (the grid has no empty tile)
+    const uint32_t x0 = blockIdx.x * PRIMARY_TILE, r0 = blockIdx.y * PRIMARY_TILE;
+    const uint32_t x1 = min(x0 + PRIMARY_TILE, F.W), r1 = min(r0 + PRIMARY_TILE, F.rows);
+    const double y_lo = (double)primary_image_row(r0, F.row_offset, F.row_stride);
+    const double y_hi = (double)primary_image_row(r1 - 1u, F.row_offset, F.row_stride);
+    const Beam tile = make_beam(C, 0.5 * ((double)x0 + (double)(x1 - 1u)), 0.5 * (y_lo + y_hi),
+                                0.5 * (double)(x1 - x0), 0.5 * (y_hi - y_lo) + 0.5);
+    for (uint32_t i = tid; i < n; i += BLK) {
+        const double4 s4 = S.spheres[i];
+        const double s[4] = {s4.x, s4.y, s4.z, s4.w};
+        if (beam_may_hit(tile, s)) atomicOr(&bits[i >> 5], 1u << (i & 31u));
+    }
+    __syncthreads();
+    const uint32_t px = x0 + tid % PRIMARY_TILE, prow = r0 + tid / PRIMARY_TILE;
+    if (px >= F.W || prow >= F.rows) return;
+    const Beam beam = make_beam(C, (double)px, (double)primary_image_row(prow, F.row_offset, F.row_stride), 0.5, 0.5);
+    // the pixel's slots, slot k in bits 16 k .. 16 k + 15 of {lo, hi}
+    constexpr uint64_t NONE4 = 0x0001000100010001ull * PRIMARY_NONE;
+    uint64_t lo = NONE4, hi = NONE4;
+    uint32_t cnt = 0;
+    for (uint32_t w = 0; w < words; ++w) {
+        uint32_t m = bits[w];
+        while (m) {
+            const uint32_t i = w * 32u + (uint32_t)__ffs((int)m) - 1u;
+            m &= m - 1u;
+            const double4 s4 = S.spheres[i];
+            const double s[4] = {s4.x, s4.y, s4.z, s4.w};
+            if (beam_may_hit(beam, s)) {
+                const uint32_t sh = (cnt & 3u) * 16u;
+                if (cnt < 4u) lo = (lo & ~(0xffffull << sh)) | ((uint64_t)i << sh);
+                else if (cnt < PRIMARY_CAP) hi = (hi & ~(0xffffull << sh)) | ((uint64_t)i << sh);
+                ++cnt;
+            }
+        }
+    }
+    if (cnt > PRIMARY_CAP) lo = (lo & ~0xffffull) | PRIMARY_WALK;
+    RT_GLOBAL uint4* dst = (RT_GLOBAL uint4*)P->cand + ((uint64_t)prow * F.W + px);
+    *dst = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
 // to_rgb of a linear f32 framebuffer already on the device (e.g. the gathered
 // multi-GPU frame).
 __global__ void __launch_bounds__(256) rt_to_rgb_kernel(const float* __restrict__ lin, uint8_t* __restrict__ srgb,
@@ -317,6 +381,8 @@ static void fill_kparams(rtk::KParams& K, const rtk::SceneView* view, const rtk_
     K.partial = partial;
     K.stats = stats;
     K.stack_ovf = (RT_GLOBAL uint2*)stack_ovf;
+    K.cand = (const RT_GLOBAL uint4*)fd->primary;
+    K.inv_stride = inv_up(F.row_stride);
 }
 
 static hipError_t launch_reduce(const rtk_frame_desc* fd, const rtk::Frame& F, double* partial, float* out,
@@ -363,6 +429,14 @@ extern "C" hipError_t rtk_launch_frame(const rtk::SceneView* view, const rtk_fra
     e = hipMemsetAsync(queue, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     if (fd->ev_start) (void)hipEventRecord((hipEvent_t)fd->ev_start, stream);
+    // the basic tier's batch variant reads its primary-ray candidates from the
+    // launch's table: filled here, inside the span the events time
+    const bool batch = tier == rtk::TIER_BASIC && view->n_nodes4 <= rtk::NODE_LDS_CAP_BATCH;
+    if (batch && fd->primary && fd->W && fd->rows) {
+        hipLaunchKernelGGL(rtk::rt_primary_kernel, dim3(rtk::primary_tiles(fd->W), rtk::primary_tiles(fd->rows)),
+                           dim3(rtk::PRIMARY_TILE * rtk::PRIMARY_TILE), 0, stream, Pd);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     // the basic tier: shading batches over trees that leave room for the
     // park area, whole-wave shading over the rest (rt_path_kernel WIDE)
     e = tier == rtk::TIER_BASIC  ? (view->n_nodes4 > rtk::NODE_LDS_CAP_BATCH ? rtk_launch_path_0w(grid, stream, Pd)

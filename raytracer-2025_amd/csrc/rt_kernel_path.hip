@@ -11,6 +11,7 @@
 #include "rt_kernel.h"
 #include "rt_math.h"
 #include "rt_slab.h"
+#include "rt_primary.h"
 #include "rt_plan.h"
 #include "rt_queue.h"
 #include "rt_path_entry.h"
@@ -257,8 +258,21 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         // that the one Philox block and sincos of the iteration's Draws serve
         // both (struct Draws).  A lane whose path ends in shading (depth,
         // panic, no scatter) starts its next sample one iteration later.
+        // That is the wide variant's iteration; the batch variant's is walk
+        // -> (miss) -> refill -> a new sample's camera draws, camera ray and
+        // candidate tests -> the vertex draws -> shade (PRIM, below).
         bool no_path = true;  // the lane starts a sample at its next post-walk stage
         constexpr int BATCH = BASIC_BATCH;
+        // Batch variant: a lane that starts a sample resolves its camera ray
+        // in the post-walk pass, by the exact sphere test on its pixel's
+        // candidates (rt_primary.h; the launch's table, P->cand), and shades
+        // a hit in the same pass with the walked hits.  The closest hit does
+        // not depend on the order of the tests, so the hit is the walk's.  A
+        // camera ray that hits nothing (`pmiss`) sits out the next walk phase
+        // and ends its sample in that iteration's miss stage; a pixel with
+        // more candidates than the table holds sends its rays through the walk.
+        constexpr bool PRIM = !WIDE;
+        bool pmiss = false;
         // ---- Camera::get_ray (camera.rs:247-273), vertex 0, from the iteration's draws
         auto camera_ray = [&](const Draws& Dr) {
             const uint32_t s_i = sie & 0xFFFFu, py = udiv_inv(rng.pixel, F.inv_W), px = rng.pixel - py * F.W;
@@ -284,7 +298,7 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
             RT_DIAG_ONLY(const unsigned long long t_loop0 = __builtin_amdgcn_s_memtime(); ++dg.main_iters;)
             RT_ISA_MARK("fields");
 #ifdef RT_WAVE_TRACE
-            hist.add(__ballot(!no_path && !walking));
+            hist.add(__ballot(!no_path && !walking && !pmiss));
 #endif
             if constexpr (TIER == TIER_BASIC && PARK) {
                 // a new walk and a walk carried over the last shading round
@@ -309,8 +323,10 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                     T.nxf = 0;
                     T.hit.nxf = 0;
                     T.nmed = 0;
-                    T.cur = no_path ? 0u : bword(S, S.world_root);
-                    if (!no_path) {
+                    // (a camera ray that missed every candidate has no walk either)
+                    const bool begin = !no_path && !pmiss;
+                    T.cur = begin ? bword(S, S.world_root) : 0u;
+                    if (begin) {
                         rng.begin(vertex);
                         ++n_rays;
                         walking = true;
@@ -374,12 +390,112 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
                 if (panic) ++n_panics;
                 finish_sample();
                 cam = true;
+                if constexpr (PRIM) pmiss = false;
             }
             RT_DIAG_ONLY(const unsigned long long t_m = __builtin_amdgcn_s_memtime(); dg.cyc_miss += t_m - t_b1;)
             RT_ISA_MARK("refill");
             if (!refill()) break;
             RT_DIAG_ONLY(const unsigned long long t_q = __builtin_amdgcn_s_memtime(); dg.cyc_queue += t_q - t_m;)
             if (carry) continue;
+            if constexpr (PRIM) {
+                // ---- a new sample: its own camera draws (vertex 0: the pixel
+                // offsets at slots 0 and 1; with a lens, theta and r at slots 2
+                // and 3 and the sincos), the camera ray, and the exact test
+                // of the pixel's candidates, which fills T.hit / T.found as
+                // the walk would have
+                RT_ISA_MARK("camera");
+                bool hit = !cam;  // the lanes the shading stages run for: walked hits, and primary hits
+                if (cam) {
+                    rng.sample = (sie & 0xFFFFu) * F.S + s_j;
+                    Draws Dc;
+                    rng.pair(0u, F.defocus ? 1u : 0u, Dc.xi0, Dc.xi1);
+                    Dc.sn = 0.0, Dc.cs = 0.0;
+                    if (F.defocus) k_sincos_2pi(Dc.xi0, &Dc.sn, &Dc.cs);
+                    camera_ray(Dc);
+                    const uint32_t py = udiv_inv(rng.pixel, F.inv_W), px = rng.pixel - py * F.W;
+                    const uint32_t prow = udiv_inv(py - F.row_offset, P->inv_stride);
+                    const RT_GLOBAL uint4* const tab = P->cand;
+                    uint4 w = make_uint4(PRIMARY_WALK, 0u, 0u, 0u);
+                    if (tab) w = tab[(uint64_t)prow * F.W + px];
+                    if ((w.x & 0xffffu) != PRIMARY_WALK) {
+                        rng.begin(vertex);  // the walk's start, without the walk
+                        ++n_rays;
+                        const double a = len2(ray.d), inva = 1.0 / a;
+                        Closest cl;
+                        cl.c = __builtin_huge_val();
+                        bool found = false;
+                        uint32_t href = 0;
+                        for (;;) {
+                            const uint32_t idx = w.x & 0xffffu;
+                            if (idx >= PRIMARY_NONE) break;
+                            // the next slot; the mark shifted in ends a full row
+                            w.x = __builtin_amdgcn_alignbit(w.y, w.x, 16u);
+                            w.y = __builtin_amdgcn_alignbit(w.z, w.y, 16u);
+                            w.z = __builtin_amdgcn_alignbit(w.w, w.z, 16u);
+                            w.w = (w.w >> 16) | (PRIMARY_WALK << 16);
+                            const double4 s4 = S.spheres[idx];
+                            RT_DIAG_ONLY(++dg.prim_tests;)
+                            double t;
+                            // (sphere.rs:77-108, the sphere rounds' own test: a
+                            // root equal to the closest one takes the hit, as there)
+                            if (sphere_t_inv(d3(s4.x, s4.y, s4.z), s4.w, ray, a, inva, 1e-8, cl.c, t)) {
+                                cl.c = t;
+                                found = true;
+                                href = make_ref(K_SPHERE, idx);
+                            }
+                        }
+#ifdef RT_CHECK
+                        {  // check build: the walk of the same ray must find the same hit
+                            Trav<TIER_BASIC> Tc;
+                            trace_begin<TIER_BASIC>(S, ray, Tc);
+                            bool wk = true;
+                            while (wk) wk = trace4_step(S, ray, Tc, stk, pq, (const RT_LDS float4*)node_lds, dg);
+                            if (Tc.found != found ||
+                                (found && __double_as_longlong(Tc.hit.t) != __double_as_longlong(cl.c)))
+                                check_fail(make_ref(K_CHECK_PRIMARY, rng.pixel & 0x0fffffffu));
+                        }
+#endif
+                        RT_DIAG_ONLY(++dg.prim_rays;)
+                        T.found = found;
+                        T.hit.t = cl.c;
+                        T.hit.ref = href;
+                        T.hit.nxf = 0;
+                        pmiss = !found;
+                        hit = found;
+                    }
+                }
+                RT_DIAG_ONLY(const unsigned long long t_c = __builtin_amdgcn_s_memtime(); dg.cyc_refill += t_c - t_b1;
+                             dg.cyc_camera += t_c - t_q;)
+                if (hit) {
+                    // the vertex's draws (slots 0 and 1) and one ray_color
+                    // level (camera.rs:275-325) at depth max_depth - vertex + 1
+                    RT_ISA_MARK("draws");
+                    Draws Dr;
+                    rng.pair(vertex, 0u, Dr.xi0, Dr.xi1);
+                    k_sincos_2pi(Dr.xi0, &Dr.sn, &Dr.cs);
+                    RT_DIAG_ONLY(const unsigned long long t_d = __builtin_amdgcn_s_memtime(); dg.cyc_refill += t_d - t_c;
+                                 dg.cyc_draws += t_d - t_c;)
+                    RT_ISA_MARK("shade");
+                    rng.begin(vertex);
+                    rng.slot = 2;  // slots 0 and 1 are Dr
+                    bool panic = false;
+                    bool end_path = shade_hit_basic(S, ray, beta, T.hit, panic, Dr);
+                    if (panic) {
+                        ++n_panics;
+                        end_path = true;
+                    }
+                    if (!end_path) {
+                        ++vertex;
+                        if (vertex > F.max_depth) end_path = true;  // depth == 0 -> BLACK (camera.rs:282-284)
+                    }
+                    if (end_path) {
+                        finish_sample();
+                        no_path = true;
+                    }
+                    RT_DIAG_ONLY(dg.cyc_shade += __builtin_amdgcn_s_memtime() - t_d;)
+                }
+                continue;
+            }
             // the iteration's draws: a hit's (vertex, slots 0 and 1) or a new
             // sample's camera draws (vertex 0: theta and r of the defocus disk
             // at slots 2 and 3, else the pixel offsets at slots 0 and 1)
@@ -651,6 +767,9 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
     atomicAdd(&g_diag[36], dg.pure_rounds);
     atomicAdd(&g_diag[37], dg.pure_lanes);
     atomicAdd(&g_diag[38], dg.pure_max_pn);
+    if (lane == 0) atomicAdd(&g_diag[61], dg.cyc_camera);
+    atomicAdd(&g_diag[62], dg.prim_rays);
+    atomicAdd(&g_diag[63], dg.prim_tests);
     for (int k = 0; k < 11; ++k) {
         atomicAdd(&g_diag[39 + k], dg.cls_rounds[k]);
         atomicAdd(&g_diag[50 + k], dg.cls_lanes[k]);

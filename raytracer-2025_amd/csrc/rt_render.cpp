@@ -25,6 +25,7 @@
 
 #include "../../include/rt_mi355x.h"
 #include "rt_kernel.h"
+#include "rt_primary.h"
 #include "rt_scene.hpp"
 
 // ---------------------------------------------------------------------------- RCCL
@@ -149,6 +150,11 @@ struct DeviceWorld {
     size_t srgb_bytes = 0;
     void* stack_ovf = nullptr;  // mesh / full tiers: traversal-stack entries beyond the LDS part
     size_t stack_ovf_bytes = 0;
+    // basic tier, batch variant: the primary-ray candidate table of the last
+    // launch (rt_primary.h; filled by every launch, never reused across them)
+    void* primary = nullptr;
+    size_t primary_bytes = 0;
+    bool primary_used = false;  // the last render's launch filled and read it
     hipStream_t own_stream = nullptr;  // for parts that do not run on the caller's stream
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     hipEvent_t ev_done = nullptr;  // after the slot's last device work (orders the next render)
@@ -199,6 +205,7 @@ static void destroy_device_world(DeviceWorld* d) {
     if (d->partial) (void)hipFree(d->partial);
     if (d->out) (void)hipFree(d->out);
     if (d->stack_ovf) (void)hipFree(d->stack_ovf);
+    if (d->primary) (void)hipFree(d->primary);
     if (d->srgb) (void)hipFree(d->srgb);
     if (d->ev_start) (void)hipEventDestroy(d->ev_start);
     if (d->ev_stop) (void)hipEventDestroy(d->ev_stop);
@@ -632,6 +639,14 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
     return (end && *end == 0 && x <= 0xFFFFFFFFul) ? (uint32_t)x : dflt;
 }
 
+// Whether a launch on this device world takes the basic tier's batch variant
+// (rtk_launch_frame picks the variant by the same node count) over spheres the
+// table's 16-bit slots can name: the launches that build the candidate table.
+static bool run_primary(const DeviceWorld* d) {
+    return d->tier == rtk::TIER_BASIC && d->view.n_nodes4 <= rtk::NODE_LDS_CAP_BATCH &&
+           d->view.n_ref[rtk::K_SPHERE] <= rtk::PRIMARY_MAX_SPHERES;
+}
+
 // Runs on the part's host thread: device world, buffers, kernel launch.
 static void run_part(rt_scene* s, RenderState* r, int32_t world, int32_t lights, const rt_camera* cam, uint64_t seed,
                      bool reference_bvh, FlatWorld& fw, Part& p) {
@@ -715,6 +730,15 @@ static void run_part(rt_scene* s, RenderState* r, int32_t world, int32_t lights,
             return fail(rc);
         srgb = d->srgb;
     }
+    // The basic tier's batch variant resolves its primary rays from a table of
+    // candidate spheres per launch pixel (rt_primary.h), which the launch
+    // fills ahead of the path kernel: the camera is this call's, so the table
+    // is too -- only its buffer is kept, like the part sums'.
+    const bool primary = run_primary(d);
+    if (primary && (rc = grow(&d->primary, d->primary_bytes, (size_t)rtk::primary_table_bytes(f.W, f.rows),
+                              "hipMalloc primary-ray candidates")) != RT_OK)
+        return fail(rc);
+    f.primary = primary && f.rows > 0 ? d->primary : nullptr;
     // order after the previous render's use of this slot's buffers, and after
     // the gather that read them
     if (d->done_recorded && (e = hipStreamWaitEvent(p.stream, d->ev_done, 0)) != hipSuccess)
@@ -742,6 +766,7 @@ static void run_part(rt_scene* s, RenderState* r, int32_t world, int32_t lights,
     if ((e = hipEventRecord(d->ev_done, p.stream)) != hipSuccess) return fail(hip_fail(e, "hipEventRecord"));
     d->done_recorded = true;
     d->ran = run;
+    d->primary_used = run && f.primary;
     d->samples = (uint64_t)f.W * f.rows * f.S * f.S;
     d->W = f.W;
     d->rows = f.rows;
@@ -1291,6 +1316,25 @@ int32_t rt_render_partials_get(rt_scene* s, double* out, uint64_t n_values) {
                 out[(pix * d->S + si) * 3 + c] = sum;
             }
     }
+    return RT_OK;
+}
+
+int32_t rt_render_primary_get(rt_scene* s, uint16_t* out, uint64_t n_values) {
+    RenderState* r = s ? s->rs : nullptr;
+    if (!r || r->n_parts != 1 || r->gathered || !r->slots[0])
+        return set_error(RT_EINVAL, "no single-device render on this scene");
+    DeviceWorld* d = r->slots[0];
+    if (!d->ran || !d->primary_used)
+        return set_error(RT_EUNSUPPORTED, "the last render built no primary-ray candidate table");
+    const uint64_t n = rtk::primary_table_slots(d->W, d->rows);
+    if (n_values != n) return set_error(RT_EINVAL, "n_values must be rows * W * " + std::to_string(rtk::PRIMARY_CAP) + " = " + std::to_string(n));
+    if (n && !out) return set_error(RT_EINVAL, "null output");
+    DeviceGuard guard;
+    (void)hipSetDevice(d->device);
+    hipError_t e = hipStreamSynchronize(d->last_stream);
+    if (e != hipSuccess) return hip_fail(e, "render (stream synchronize)");
+    if (n && (e = hipMemcpy(out, d->primary, n * sizeof(uint16_t), hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy primary-ray candidates");
     return RT_OK;
 }
 

@@ -37,7 +37,7 @@ elif wl == "c5":
 else:
     world, lights, cam = scenes.random_spheres(scene, 1920, spp)
 cam.render(world, lights, seed=1, want_srgb=False)  # warm-up + flatten
-buf = (ctypes.c_ulonglong * 61)()
+buf = (ctypes.c_ulonglong * 64)()  # RT_DIAG_N (a library from before the candidate table fills 61)
 lib.rt_diag_counters(buf, 1)
 _, _, st = cam.render(world, lights, seed=1, want_srgb=False)
 lib.rt_diag_counters(buf, 0)
@@ -97,6 +97,14 @@ out = {
                              for k, name in enumerate(("miss", "lambertian_solid", "lambertian_checker",
                                                        "lambertian_image", "lambertian_noise", "lambertian_sky",
                                                        "metal", "dielectric", "diffuse_light", "isotropic", "other"))},
-    "raw": c[:61],
+    # basic tier, batch variant: the camera stage (camera draws, camera ray,
+    # candidate tests) as a share of all wave cycles -- part of refill+camera --
+    # the share of rays resolved from the candidate table instead of a walk,
+    # and the exact tests such a ray ran
+    "camera_stage_share": c[61] / tot,
+    "rays_from_table_share": c[62] / c[8],
+    "exact_tests_per_table_ray": c[63] / c[62] if c[62] else None,
+    "wave_main_iters_per_sample": c[4] / st.samples,
+    "raw": c[:64],
 }
 print(json.dumps(out, indent=1))
