@@ -121,6 +121,18 @@ void rt_disney_params_default(rt_disney_params* params);
  * set that makes NaNs is counted in rt_stats.panics like every other
  * reference assert. */
 int32_t rt_mat_disney(rt_scene* s, int32_t base_color_tex, const rt_disney_params* params);
+/* Portal::new(attenuation, position_offset, rotation) (material/portal.rs:15-25):
+ * scatter is ScatterRecord::Ray((attenuation, Ray::new_with_time(rec.p +
+ * position_offset, rotation.rotate_vector(r_in.direction), r_in.time))), so a
+ * hit costs no draw and takes no light sampling (camera.rs:317-319); emitted is
+ * black.  Null offset3 = zero, null quat_wxyz = the identity, as
+ * rt_transform_new's nulls.  RT_EINVAL: a null scene, a null attenuation, any
+ * non-finite value.  Nothing else is checked, as the reference checks nothing:
+ * the quaternion is used as given -- a zero or non-unit one is accepted and is
+ * not normalised, nor is the rotated direction -- and a direction that cannot
+ * be normalised downstream is counted in rt_stats.panics like every other
+ * reference expect. */
+int32_t rt_mat_portal(rt_scene* s, const double attenuation[3], const double* offset3, const double* quat_wxyz);
 
 /* ---- Hittables ------------------------------------------------------------ */
 /* Sphere::new (shapes/sphere.rs:25-35) */
@@ -250,8 +262,9 @@ typedef struct rt_world_info {
     uint32_t stack_need;      /* traversal-stack entries one lane needs */
     uint32_t kernel_tier;     /* 0 = spheres/BVH/basic materials, 1 = + quads/triangles/OBJ, 2 = full,
                                * 3 = full without BVH nodes, 4 = full + general lights / nested
-                               * wrapper materials, 5 = 4 + the Disney BSDF (rt_kernel.h Tier) */
-    uint32_t features;        /* F_* bits (rt_layout.h) */
+                               * wrapper materials, 5 = 4 + the Disney BSDF (rt_kernel.h Tier).
+                               * A Portal material takes tier 4, or 5 beside a Disney material */
+    uint32_t features;        /* F_* bits (rt_layout.h); 2048 = F_PORTAL: a Portal material is reachable */
 } rt_world_info;
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, uint32_t flags,
                           rt_world_info* out);

@@ -137,6 +137,7 @@ SIGNATURES = {
     "mat_mix_image": (_I, [_P, _I, _I, _I]),
     "disney_params_default": (None, [C.POINTER(RtDisneyParams)]),
     "mat_disney": (_I, [_P, _I, C.POINTER(RtDisneyParams)]),
+    "mat_portal": (_I, [_P, _DP, _DP, _DP]),
     "sphere": (_I, [_P, _DP, _D, _I]),
     "sphere_moving": (_I, [_P, _DP, _DP, _D, _I]),
     "quad": (_I, [_P, _DP, _DP, _DP, _I]),
@@ -181,7 +182,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -60,7 +60,9 @@ namespace rtk {
 //         BVH code, which leaves the registers to the rest (fewer spills).
 //  FULL_GL: FULL with general lights (Transforms, nested lists, moving
 //         spheres in the lights tree); kept apart so that the light-tree
-//         code does not weigh on the C3 / C5 tiers.
+//         code does not weigh on the C3 / C5 tiers.  With FULL_DS it
+//         also holds the Portal material (M_PORTAL, F_PORTAL): one arm of
+//         shade() beside M_TRANSPARENT, in no tier a benchmark workload runs.
 //  FULL_DS: FULL_GL with the Disney BSDF (rt_disney.h): the one tier whose
 //         shade() holds M_DISNEY, so that no other tier pays for it.
 enum Tier : int { TIER_BASIC = 0, TIER_MESH = 1, TIER_FULL = 2, TIER_FULL_FLAT = 3, TIER_FULL_GL = 4, TIER_FULL_DS = 5 };

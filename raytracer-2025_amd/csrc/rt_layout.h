@@ -166,13 +166,14 @@ enum MatType : int32_t {
     M_TRANSPARENT = 6,
     M_MIX = 7,
     M_DISNEY = 8,
+    M_PORTAL = 9,
 };
 
 // material.rs: one record per Arc<dyn Material>
 struct alignas(16) DMaterial {
     int32_t type;
     int32_t tex;       // albedo / attenuation / emission texture
-    int32_t inner;     // DiffuseLight inner material, Mix mat1; Disney: its DDisney record
+    int32_t inner;     // DiffuseLight inner material, Mix mat1; Disney / Portal: its DDisney / DPortal record
     int32_t inner2;    // Mix mat2
     double albedo[3];  // Metal albedo; the solid texture's colour (MF_SOLID)
     double fuzz;       // Metal fuzz (clamped), Dielectric ior, Mix ratio
@@ -192,6 +193,16 @@ struct alignas(16) DDisney {
     int32_t pad[3];
 };
 static_assert(sizeof(DDisney) == 112, "DDisney must be 112 B (7 dwordx4)");
+
+// Portal (material/portal.rs:9-25): the record DMaterial::inner of an M_PORTAL
+// material indexes.  The quaternion is the caller's, not normalised, as the
+// reference rotates with it as given
+struct alignas(16) DPortal {
+    double attenuation[3];
+    double offset[3];
+    double q[4];  // w, x, y, z
+};
+static_assert(sizeof(DPortal) == 80, "DPortal must be 80 B (5 dwordx4)");
 
 enum TexType : int32_t {
     T_SOLID = 0,
@@ -220,7 +231,10 @@ struct alignas(16) DPerlin {
 
 // Everything the kernel reads about the world, as device pointers.
 struct SceneView {
-    const RT_GLOBAL DNode* nodes;            // unused (no kernel walks the two-box nodes): always empty
+    // Portal records (DMaterial::inner of M_PORTAL).  In the slot of the two-box
+    // node table, which was always empty (every BVH tier walks nodes4), not
+    // appended, for the reason given at `disney` below
+    const RT_GLOBAL DPortal* portals;
     const RT_GLOBAL DNode4* nodes4;          // 4-wide nodes: K_BVH refs index these
     const RT_GLOBAL double4* spheres;        // {cx, cy, cz, r}
     const RT_GLOBAL int32_t* sphere_mat;
@@ -282,6 +296,7 @@ enum : uint32_t {
                        // DiffuseLight / Mix wrappers, Mix::from_image ratios
     F_NORMALMAP = 256u,  // ... with a normal map (full tier: image textures)
     F_DISNEY = 1024u,    // tier FULL_DS: a Disney material (rt_disney.h)
+    F_PORTAL = 2048u,    // a Portal material: tier FULL_GL, or FULL_DS beside F_DISNEY (shade()'s M_PORTAL)
 };
 
 }  // namespace rtk

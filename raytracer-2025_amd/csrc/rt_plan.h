@@ -21,7 +21,7 @@ namespace plan {
 inline int tier_for(uint32_t features) {
     const uint32_t full = F_XFORM | F_MEDIUM | F_MSPHERE | F_LIGHTS | F_TEXFULL | F_MATFULL | F_NORMALMAP;
     if (features & F_DISNEY) return 5;           // TIER_FULL_DS
-    if (features & F_GENERAL) return 4;          // TIER_FULL_GL
+    if (features & (F_GENERAL | F_PORTAL)) return 4;  // TIER_FULL_GL (M_PORTAL: shade()'s general tiers)
     if (features & full) return 2;               // TIER_FULL
     if (features & (F_PLANAR | F_REMAP)) return 1;  // TIER_MESH
     return 0;  // TIER_BASIC

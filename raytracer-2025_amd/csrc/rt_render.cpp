@@ -128,10 +128,11 @@ struct DeviceWorld {
     int32_t world = -1, lights = -1, background = -1;
     uint64_t generation = ~0ull;
     bool reference_bvh = false;
-    // a Disney world flattened for rt_world_hit / rt_world_occluded: laid out
-    // for the tier it takes without F_DISNEY (build_flat), so not a render's
+    // a Disney or Portal world flattened for rt_world_hit / rt_world_occluded:
+    // laid out for the tier it takes without F_DISNEY and F_PORTAL (build_flat),
+    // so not a render's
     bool query_flat = false;
-    bool has_disney = false;  // the world as flattened holds a Disney material
+    bool has_disney = false;  // the world as flattened holds a Disney or a Portal material
     char* blob = nullptr;
     size_t blob_bytes = 0;
     rtk::SceneView view{};
@@ -332,7 +333,9 @@ static size_t put(std::vector<char>& blob, const std::vector<T>& v) {
 // into it.
 static void pack_world(const HostWorld& hw, std::vector<char>& blob, rtk::SceneView& v) {
     auto off = [](size_t o) { return (uintptr_t)o; };
-    v.nodes = (const rtk::DNode*)off(put(blob, hw.nodes));
+    // (first, where the two-box node table, always empty by now, was put: a
+    // world without a portal packs to the bytes it always did)
+    v.portals = (const rtk::DPortal*)off(put(blob, hw.portals));
     v.nodes4 = (const rtk::DNode4*)off(put(blob, hw.nodes4));
     v.spheres = (const double4*)off(put(blob, hw.spheres));
     v.sphere_mat = (const int32_t*)off(put(blob, hw.sphere_mat));
@@ -375,10 +378,10 @@ struct FlatWorld {
     rtk::SceneView rel{};  // SceneView with byte offsets into blob instead of pointers
     size_t n_prims = 0;
     // for_query: the world of a hit / occlusion query.  Materials do not reach
-    // those kernels, so a Disney world takes the tier, and with it the node
-    // format, it would take without F_DISNEY
+    // those kernels, so a Disney or Portal world takes the tier, and with it
+    // the node format, it would take without F_DISNEY and F_PORTAL
     bool for_query = false;
-    bool has_disney = false;
+    bool has_disney = false;  // ... or a Portal
 };
 
 static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg, bool reference_bvh, FlatWorld& fw) {
@@ -391,8 +394,8 @@ static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg
     auto t0 = std::chrono::steady_clock::now();
     HostWorld hw;
     int32_t rc = flatten(s, world, lights, bg, reference_bvh, hw);
-    fw.has_disney = rc == RT_OK && (hw.features & rtk::F_DISNEY) != 0;
-    if (fw.for_query) hw.features &= ~rtk::F_DISNEY;
+    fw.has_disney = rc == RT_OK && (hw.features & (rtk::F_DISNEY | rtk::F_PORTAL)) != 0;
+    if (fw.for_query) hw.features &= ~(rtk::F_DISNEY | rtk::F_PORTAL);
     int tier = rc == RT_OK ? prepare_tier(hw) : -1;
     if (rc == RT_OK && tier < 0) rc = RT_ESTACK;
 #ifdef RT_CHECK
@@ -531,7 +534,7 @@ static int32_t upload_world(rt_scene* s, DeviceWorld* d, int32_t world, int32_t 
     char* b = d->blob;
     rtk::SceneView v = fw.rel;
     auto fix = [b](auto& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + (uintptr_t)p); };
-    fix(v.nodes), fix(v.nodes4), fix(v.spheres), fix(v.sphere_mat), fix(v.sphere_rinv), fix(v.msph_center), fix(v.msph_dir),
+    fix(v.portals), fix(v.nodes4), fix(v.spheres), fix(v.sphere_mat), fix(v.sphere_rinv), fix(v.msph_center), fix(v.msph_dir),
         fix(v.msph_mat), fix(v.planars), fix(v.planar_area), fix(v.planar_mat), fix(v.planar_remap), fix(v.remaps),
         fix(v.remap_nm), fix(v.list_children), fix(v.list_boxes), fix(v.xforms), fix(v.media), fix(v.materials), fix(v.textures),
         fix(v.texels), fix(v.perlin), fix(v.disney);

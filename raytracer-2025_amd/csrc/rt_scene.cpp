@@ -948,13 +948,14 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
         rtk::DMaterial m{};
         m.type = r.type;
         m.tex = r.tex;
-        m.inner = r.type == rtk::M_DISNEY ? r.disney : r.inner;
+        m.inner = r.type == rtk::M_DISNEY ? r.disney : r.type == rtk::M_PORTAL ? r.portal : r.inner;
         m.inner2 = r.inner2;
         for (int k = 0; k < 3; ++k) m.albedo[k] = r.albedo[k];
         m.fuzz = r.param;
         out.materials.push_back(m);
     }
     out.disney = s->disneys;
+    out.portals = s->portals;
     // flags: uv need and emission, resolved through DiffuseLight/Mix nesting
     for (size_t i = 0; i < out.materials.size(); ++i) {
         rtk::DMaterial& m = out.materials[i];
@@ -1016,7 +1017,8 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
     while (!work.empty()) {
         const int m = work.back();
         work.pop_back();
-        if (out.materials[m].type == rtk::M_DISNEY) continue;  // (its inner is a DDisney record)
+        // (a Disney's or a Portal's inner is its DDisney / DPortal record)
+        if (out.materials[m].type == rtk::M_DISNEY || out.materials[m].type == rtk::M_PORTAL) continue;
         use_mat(out.materials[m].inner);
         use_mat(out.materials[m].inner2);
     }
@@ -1049,6 +1051,8 @@ int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t backgr
             m.type == rtk::M_MIX)
             out.features |= rtk::F_MATFULL;
         if (m.type == rtk::M_DISNEY) out.features |= rtk::F_DISNEY;
+        // (reachable: a portal under Mix / DiffuseLight wrappers is marked by the walk above)
+        if (m.type == rtk::M_PORTAL) out.features |= rtk::F_PORTAL;
     }
     // Wrapper materials (DiffuseLight with a material, Mix): the C3 / C5 tiers
     // take one level whose Mix ratio is a constant; deeper trees and
@@ -1337,6 +1341,29 @@ int32_t rt_mat_disney(rt_scene* s, int32_t tex, const rt_disney_params* p) {
     m.type = rtk::M_DISNEY;
     m.tex = tex;
     m.disney = (int)s->disneys.size() - 1;
+    return push_mat(s, m);
+}
+
+// Portal::new (material/portal.rs:15-25).  Nothing but finiteness is checked,
+// as the reference checks nothing: the quaternion is kept as given
+int32_t rt_mat_portal(rt_scene* s, const double attenuation[3], const double* offset3, const double* quat_wxyz) {
+    if (!s || bad(attenuation)) return set_error(RT_EINVAL, "null argument");
+    rtk::DPortal d{};
+    d.q[0] = 1.0;  // Quaternion::identity (quaternion.rs:14-21)
+    for (int k = 0; k < 3; ++k) d.attenuation[k] = attenuation[k];
+    if (offset3)
+        for (int k = 0; k < 3; ++k) d.offset[k] = offset3[k];
+    if (quat_wxyz)
+        for (int k = 0; k < 4; ++k) d.q[k] = quat_wxyz[k];
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(d.attenuation[k]) || !std::isfinite(d.offset[k]))
+            return set_error(RT_EINVAL, "non-finite Portal parameter");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(d.q[k])) return set_error(RT_EINVAL, "non-finite Portal parameter");
+    s->portals.push_back(d);
+    MatRec m{};
+    m.type = rtk::M_PORTAL;
+    m.portal = (int)s->portals.size() - 1;
     return push_mat(s, m);
 }
 

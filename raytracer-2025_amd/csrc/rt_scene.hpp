@@ -104,6 +104,7 @@ struct MatRec {
     double albedo[3] = {0, 0, 0};
     double param = 0;
     int disney = -1;  // M_DISNEY: index into rt_scene::disneys
+    int portal = -1;  // M_PORTAL: index into rt_scene::portals
 };
 
 // Flattened world on the host, ready to upload as one blob.
@@ -130,6 +131,7 @@ struct HostWorld {
     std::vector<float> texels;
     std::vector<rtk::DPerlin> perlin;
     std::vector<rtk::DDisney> disney;  // the records DMaterial::inner of an M_DISNEY material indexes
+    std::vector<rtk::DPortal> portals;  // ... and of an M_PORTAL material
     uint32_t world_root = 0, lights_root = 0;
     uint32_t stack_need = 0;
     uint32_t features = 0;
@@ -148,6 +150,7 @@ struct rt_scene {
     std::vector<float> texels;
     std::vector<rtk::DPerlin> perlins;
     std::vector<rtk::DDisney> disneys;
+    std::vector<rtk::DPortal> portals;
     uint32_t next_medium_id = 0;
     uint64_t generation = 0;  // bumped by every mutation; invalidates the device cache
     // device-side cache and the last render's state (rt_render.cpp)

@@ -254,6 +254,18 @@ __device__ __forceinline__ bool shade(const SceneView& S, Ray& ray, D3& beta, D3
                     break;
                 }
             }
+            if constexpr (tier_general(TIER)) {
+                // Portal::scatter (portal.rs:15-30): ScatterRecord::Ray, so no draw and no
+                // PDF (camera.rs:317-319); the quaternion and the rotated direction are
+                // used as they come.  The record is read here only
+                if (M.type == M_PORTAL) {
+                    const DPortal P = S.portals[M.inner];
+                    beta = beta * d3(P.attenuation[0], P.attenuation[1], P.attenuation[2]);
+                    ray = Ray{rec.p + d3(P.offset[0], P.offset[1], P.offset[2]),
+                              quat_rotate(P.q[0], P.q[1], P.q[2], P.q[3], ray.d), ray.time};
+                    break;
+                }
+            }
             return true;
     }
     if (pdf_kind >= 0) {

@@ -172,6 +172,16 @@ class Scene:
         p = self.disney_params(**params)
         return Material(self, self._c(self.api.mat_disney(self.s, tex.h, C.byref(p))))
 
+    def Portal(self, attenuation, offset=None, rotation=None):
+        """Portal::new(attenuation, position_offset, rotation)
+        (material/portal.rs:15-25): the ray goes on from rec.p + offset along
+        rotation.rotate_vector(direction), tinted by `attenuation`.  `rotation`
+        is a Quaternion, used as given (not normalised); None = identity,
+        offset None = zero."""
+        off = d3(offset) if offset is not None else None
+        q = d4(rotation.wxyz) if rotation is not None else None
+        return Material(self, self._c(self.api.mat_portal(self.s, d3(attenuation), off, q)))
+
     # ---- hittables
     def Sphere(self, center, radius, mat):
         return Hittable(self, self._c(self.api.sphere(self.s, d3(center), float(radius), mat.h)), "sphere")

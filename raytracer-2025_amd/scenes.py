@@ -253,3 +253,34 @@ def obj_terrain(scene, obj_path, image_width=1920, samples_per_pixel=256, max_de
     cam.focus_distance = 10.0
     cam.background = scene.SkyGradient((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))
     return world, None, cam
+
+
+def portal_scene(scene, background=None, image_width=1920, samples_per_pixel=500, max_depth=10, quad_material=None):
+    """src/main.rs:50-90 portal_scene(): a Portal(WHITE, (2, 0, 0), identity)
+    quad in the y = 0 plane and a white Lambertian sphere below the place its
+    offset leads to, 16:9, ACES tone map.
+
+    The reference lights it with an EXR image texture
+    (rogland_clear_night_4k.exr), which no decoder here reads, so the
+    background is a parameter: any Texture, by default the sky gradient of the
+    other scenes.  quad_material puts another material in the Portal's place
+    (Transparent: the same kernel tier's cost without the Portal arm,
+    scripts/portal_rate.py)."""
+    if quad_material is None:
+        quad_material = scene.Portal((1.0, 1.0, 1.0), (2.0, 0.0, 0.0), Quaternion.identity())
+    world = scene.Hittables()
+    world.add(scene.Quad((-1.0, 0.0, -1.0), (0.0, 0.0, 2.0), (2.0, 0.0, 0.0), quad_material))
+    world.add(scene.Sphere((2.0, -1.5, 0.0), 1.0, scene.Lambertian(scene.SolidColor((1.0, 1.0, 1.0)))))
+    cam = Camera()
+    cam.aspect_ratio = 16.0 / 9.0
+    cam.image_width = image_width
+    cam.samples_per_pixel = samples_per_pixel
+    cam.max_depth = max_depth
+    cam.vertical_fov_in_degrees = 40.0
+    cam.look_from = (0.0, 4.0, 2.0)  # Point3::new(0.0, 2.0, 1.0) * 2.0, exact
+    cam.look_at = (0.0, 0.0, 0.0)
+    cam.vec_up = (0.0, 1.0, 0.0)
+    cam.defocus_angle_in_degrees = 0.0
+    cam.toon_map = 1  # ToonMap::ACES
+    cam.background = background if background is not None else scene.SkyGradient((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))
+    return world, None, cam
