@@ -350,6 +350,73 @@ int32_t rt_world_occluded(rt_scene* s, int32_t world, uint64_t seed, uint32_t fl
 int32_t rt_world_occluded_device(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays_device,
                                  uint64_t n, uint8_t* out_device, void* stream);
 
+/* ---- Radiance queries: Camera::ray_color for caller-given rays ---------------- */
+/* The shading half of the path, open to any ray: an orthographic, fisheye or
+ * equirectangular view, a light probe, a lightmap texel, a re-trace of a few
+ * pixels, a host-side integrator that wants the radiance along a ray. */
+typedef struct rt_radiance_opts {
+    uint32_t struct_size;   /* set by rt_radiance_opts_default; fields only ever appended */
+    uint32_t max_depth;     /* Camera.max_depth; 0 -> every result BLACK (camera.rs:282-284) */
+    uint64_t seed;          /* RNG key (oracle/rng_contract.hpp) */
+    uint32_t samples;       /* ray_color evaluations per ray, >= 1 */
+    uint32_t flags;         /* RT_FLAG_REFERENCE_BVH or 0 */
+    int32_t background_tex; /* Camera.background; -1 = BLACK */
+    uint32_t first_index;   /* RNG pixel of ray 0; ray i uses first_index + i */
+    void* stream;           /* device variant only; NULL = default stream */
+} rt_radiance_opts;
+/* max_depth 10, samples 1, background_tex -1, everything else 0 */
+void rt_radiance_opts_default(rt_radiance_opts* opts);
+
+typedef struct rt_radiance {
+    double rgb[3];   /* (sum over s of ray_color_s) * (1.0 / samples), f64 */
+    uint32_t rays;   /* ray_color calls that reached world.hit, all samples */
+    uint32_t panics; /* samples that met a reference assert / expect / NaN */
+} rt_radiance;       /* 32 B */
+
+/* For ray i of n and each sample s < opts->samples,
+ *     Camera::ray_color(Ray{origin, dir, time}, max_depth, world, lights)
+ * (camera.rs:275-325) with Camera.background = background_tex; the direction
+ * is used as given (not normalised).  Over every world rt_render accepts:
+ * lights, media, wrapper materials, Disney and Portal included.
+ * RNG: the contract's main and medium streams (oracle/rng_contract.hpp) keyed
+ * (seed, pixel = first_index + i, sample = s, vertex = k) for the k-th
+ * ray_color call along the path, k >= 1 -- what rt_render draws from vertex 1
+ * on; vertex 0 (the camera ray's draws) is not used.
+ * The samples are summed in f64 in ascending s from zero and the sum is
+ * multiplied once by 1.0 / samples: the result does not depend on scheduling.
+ * t_max bounds the first world.hit only, the interval [1e-8, t_max] with both
+ * ends inclusive: a first hit past it is a miss and the background is
+ * returned; later vertices use [1e-8, inf), and t_max = +inf is plain
+ * ray_color.
+ * A sample that panics (a reference assert / expect, or a NaN result) ends
+ * there and adds what rt_render would have added for it -- the radiance
+ * gathered so far, or black if that is NaN (camera.rs:323) -- and counts once
+ * in `panics`.
+ * RT_EINVAL: a null scene or opts; a null array with n > 0; struct_size below
+ * this version's; samples == 0; unknown flags; first_index + n > 2^32; (no
+ * max_depth is refused: rt_render refuses none); in the host variant a ray
+ * with a non-finite origin, direction or time, a zero direction, or a NaN or
+ * negative t_max, named in rt_last_error as rt_world_hit names it.
+ * RT_EHANDLE / RT_EMOVED / RT_EUNSUPPORTED / RT_ESTACK as rt_render gives them
+ * for (world, lights, background_tex).  RT_EDEVICE without a gfx950 device
+ * (there is no CPU fallback).  n == 0 is RT_OK, touches no device and needs
+ * no arrays.  max_depth == 0 with n > 0 writes zeros without a kernel launch.
+ * The world is flattened and uploaded as for rt_render(world, lights,
+ * background_tex, flags) -- not as for rt_world_hit, whose flattening drops
+ * what only materials need -- and shares the scene's per-device world cache
+ * with renders: a render and a radiance query of one flattening upload once.
+ * The device work is ordered after the scene's previous device work, as
+ * renders are.  Host arrays, on the calling thread's current device,
+ * blocking: */
+int32_t rt_world_radiance(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* opts, const rt_ray* rays,
+                          uint64_t n, rt_radiance* out);
+/* The same from and to gfx950 device arrays, enqueued on opts->stream without
+ * waiting (max_depth == 0: a memset).  The rays are the caller's duty, as in
+ * rt_world_hit_device; the kernel ends and writes a record for any ray, and
+ * none past out_device[n - 1]. */
+int32_t rt_world_radiance_device(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* opts,
+                                 const rt_ray* rays_device, uint64_t n, rt_radiance* out_device);
+
 /* Number of rows a shard renders (rows of the compact output). */
 uint32_t rt_shard_rows(const rt_camera* cam, const rt_render_opts* opts);
 

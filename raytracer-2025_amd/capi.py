@@ -108,6 +108,32 @@ class RtHitRecord(C.Structure):
 
 HIT_FOUND, HIT_FRONT_FACE, HIT_MEDIUM = 1, 2, 4
 
+
+class RtRadianceOpts(C.Structure):
+    """rt_radiance_opts -- the options of rt_world_radiance (made by rt_radiance_opts_default)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("samples", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("background_tex", C.c_int32),
+        ("first_index", C.c_uint32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class RtRadiance(C.Structure):
+    """rt_radiance -- the result of one query ray of rt_world_radiance (32 B)."""
+
+    _fields_ = [
+        ("rgb", c_double3),
+        ("rays", C.c_uint32),
+        ("panics", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _U = C.c_uint32
@@ -160,6 +186,10 @@ SIGNATURES = {
     "world_hit_device": (_I, [_P, _I, C.c_uint64, _U, _P, C.c_uint64, _P, _P]),
     "world_occluded": (_I, [_P, _I, C.c_uint64, _U, C.POINTER(RtRay), C.c_uint64, C.POINTER(C.c_uint8)]),
     "world_occluded_device": (_I, [_P, _I, C.c_uint64, _U, _P, C.c_uint64, _P, _P]),
+    "radiance_opts_default": (None, [C.POINTER(RtRadianceOpts)]),
+    "world_radiance": (_I, [_P, _I, _I, C.POINTER(RtRadianceOpts), C.POINTER(RtRay), C.c_uint64,
+                            C.POINTER(RtRadiance)]),
+    "world_radiance_device": (_I, [_P, _I, _I, C.POINTER(RtRadianceOpts), _P, C.c_uint64, _P]),
     "shard_rows": (_U, [C.POINTER(RtCamera), C.POINTER(RtRenderOpts)]),
     "render_device": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), _P]),
     "render_device_wait": (_I, [_P, C.POINTER(RtStats)]),
@@ -182,7 +212,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -1,6 +1,6 @@
 // rt_kernel.h -- interface between the host render driver (rt_render.cpp) and
 // the gfx950 kernels (rt_kernel_path.hip, rt_kernel_hit.hip,
-// rt_kernel_occl.hip, rt_kernel_common.hip).
+// rt_kernel_occl.hip, rt_kernel_radiance.hip, rt_kernel_common.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,6 +170,17 @@ extern "C" __attribute__((weak)) hipError_t rtk_launch_hits(const rtk::SceneView
 extern "C" __attribute__((weak)) hipError_t rtk_launch_occluded(const rtk::SceneView* view, const struct rt_ray* rays,
                                                                 uint8_t* out, uint64_t n, uint64_t seed, int tier,
                                                                 int grid, void* stack_ovf, hipStream_t stream);
+// rt_world_radiance's kernel: Camera::ray_color of each of n rays (device
+// arrays), `samples` times, one rt_radiance a ray; the Rng pixel of ray i is
+// first_index + i.  `counter`: one device word of the scene's work buffers
+// (the kernel's ray counter, zeroed on the stream by the call).  All six
+// tiers; grid and weakness as rtk_launch_hits.
+struct rt_radiance;
+extern "C" __attribute__((weak)) hipError_t rtk_launch_radiance(const rtk::SceneView* view, const struct rt_ray* rays,
+                                                                struct rt_radiance* out, uint64_t n, uint64_t seed,
+                                                                uint32_t first_index, uint32_t samples,
+                                                                uint32_t max_depth, uint32_t* counter, int tier, int grid,
+                                                                void* stack_ovf, hipStream_t stream);
 // The Disney self-test (rt_disney_selftest): fn's doubles per case in and out
 // (0 for an unknown fn), and n cases of the BSDF's device functions as the
 // path kernel's Disney tier compiles them.  Weak as rtk_launch_hits is: absent

@@ -810,9 +810,9 @@ static int32_t root_buffers(RenderState* r, int device, size_t staging_bytes, si
 // Rows of part k of n of a shard with `rows` compact rows (rows k, k+n, ...).
 static inline uint32_t part_rows(uint32_t rows, uint32_t k, uint32_t n) { return k >= rows ? 0 : (rows - k + n - 1) / n; }
 
-static int32_t validate(rt_scene* s, int32_t world, int32_t lights, const rt_camera* cam) {
-    if (!s) return set_error(RT_EINVAL, "null scene");
-    if (!cam) return set_error(RT_EINVAL, "null camera");
+// The handle checks of a render of (world, lights, background texture); a
+// radiance query's are the same
+static int32_t validate_handles(rt_scene* s, int32_t world, int32_t lights, int32_t background_tex) {
     if (world < 0 || (size_t)world >= s->objs.size() || s->objs[world].hidden)
         return set_error(RT_EHANDLE, "unknown world handle");
     if (s->objs[world].moved) return set_error(RT_EMOVED, "world handle was moved");
@@ -821,9 +821,15 @@ static int32_t validate(rt_scene* s, int32_t world, int32_t lights, const rt_cam
             return set_error(RT_EHANDLE, "unknown lights handle");
         if (s->objs[lights].moved) return set_error(RT_EMOVED, "lights handle was moved");
     }
-    if (cam->background_tex != -1 && (cam->background_tex < 0 || (size_t)cam->background_tex >= s->texs.size()))
+    if (background_tex != -1 && (background_tex < 0 || (size_t)background_tex >= s->texs.size()))
         return set_error(RT_EHANDLE, "unknown background texture");
     return RT_OK;
+}
+
+static int32_t validate(rt_scene* s, int32_t world, int32_t lights, const rt_camera* cam) {
+    if (!s) return set_error(RT_EINVAL, "null scene");
+    if (!cam) return set_error(RT_EINVAL, "null camera");
+    return validate_handles(s, world, lights, cam->background_tex);
 }
 
 // Enqueues one render (all parts, and the gather when there is more than one
@@ -1119,6 +1125,44 @@ static int32_t hit_args(rt_scene* s, int32_t world, uint32_t flags, const void* 
     return RT_OK;
 }
 
+// The ray checks of the queries' host variants: the first bad ray by its index
+static int32_t check_rays(const rt_ray* rays, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const rt_ray& q = rays[i];
+        bool ok = std::isfinite(q.time) && q.t_max >= 0.0;  // (a NaN t_max fails the compare)
+        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(q.origin[k]) && std::isfinite(q.dir[k]);
+        ok = ok && (q.dir[0] != 0.0 || q.dir[1] != 0.0 || q.dir[2] != 0.0);
+        if (!ok)
+            return set_error(RT_EINVAL, "ray " + std::to_string(i) +
+                                            ": non-finite origin, direction or time, zero direction, or NaN / negative t_max");
+    }
+    return RT_OK;
+}
+
+// A query's slot: slot 0's device world on the current device, as renders use it
+static int32_t query_slot(rt_scene* s, DeviceWorld*& d) {
+    int cur = -1;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
+    if (!s->rs) s->rs = new RenderState();
+    RenderState* r = s->rs;
+    if (r->slots.empty()) r->slots.resize(1, nullptr);
+    // a slot on another device is made anew, and the last render's state on
+    // it (rt_render_device_wait) goes with it
+    if (r->slots[0] && r->slots[0]->device != cur) r->n_parts = 0;
+    return slot_for(r, 0, cur, d);
+}
+
+// Orders `stream` after the slot's previous device work and the gather that read it
+static int32_t query_order(RenderState* r, DeviceWorld* d, hipStream_t stream) {
+    hipError_t e;
+    if (d->done_recorded && (e = hipStreamWaitEvent(stream, d->ev_done, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    if (r->g_recorded && (e = hipStreamWaitEvent(stream, r->g_stop, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    return RT_OK;
+}
+
 // What a query writes for a ray: rt_world_hit's record or rt_world_occluded's byte
 enum QueryKind { Q_RECORD, Q_OCCLUDED };
 static size_t query_out_bytes(QueryKind k) { return k == Q_RECORD ? sizeof(rt_hit_record) : sizeof(uint8_t); }
@@ -1134,24 +1178,15 @@ static int32_t hit_enqueue(rt_scene* s, int32_t world, uint64_t seed, uint32_t f
     if (kind == Q_RECORD && !rtk_launch_hits) return set_error(RT_EUNSUPPORTED, "this build holds no hit-query kernels");
     if (kind == Q_OCCLUDED && !rtk_launch_occluded)
         return set_error(RT_EUNSUPPORTED, "this build holds no occlusion-query kernels");
-    if (!s->rs) s->rs = new RenderState();
-    RenderState* r = s->rs;
-    if (r->slots.empty()) r->slots.resize(1, nullptr);
-    // a slot on another device is made anew, and the last render's state on
-    // it (rt_render_device_wait) goes with it
-    if (r->slots[0] && r->slots[0]->device != cur) r->n_parts = 0;
     DeviceWorld* d = nullptr;
-    int32_t rc = slot_for(r, 0, cur, d);
+    int32_t rc = query_slot(s, d);
     if (rc != RT_OK) return rc;
     FlatWorld fw;
     fw.for_query = true;
     double flatten_ms = 0;
     if ((rc = upload_world(s, d, world, -1, -1, (flags & RT_FLAG_REFERENCE_BVH) != 0, fw, flatten_ms)) != RT_OK)
         return rc;
-    if (d->done_recorded && (e = hipStreamWaitEvent(stream, d->ev_done, 0)) != hipSuccess)
-        return hip_fail(e, "hipStreamWaitEvent");
-    if (r->g_recorded && (e = hipStreamWaitEvent(stream, r->g_stop, 0)) != hipSuccess)
-        return hip_fail(e, "hipStreamWaitEvent");
+    if ((rc = query_order(s->rs, d, stream)) != RT_OK) return rc;
     e = kind == Q_RECORD ? rtk_launch_hits(&d->view, rays_dev, (rt_hit_record*)out_dev, n, seed, d->tier,
                                            d->grid[d->tier], d->stack_ovf, stream)
                          : rtk_launch_occluded(&d->view, rays_dev, (uint8_t*)out_dev, n, seed, d->tier,
@@ -1180,15 +1215,7 @@ static int32_t query_host(rt_scene* s, int32_t world, uint64_t seed, uint32_t fl
                           QueryKind kind, void* out) {
     int32_t rc = hit_args(s, world, flags, rays, n, out);
     if (rc != RT_OK || n == 0) return rc;
-    for (uint64_t i = 0; i < n; ++i) {
-        const rt_ray& q = rays[i];
-        bool ok = std::isfinite(q.time) && q.t_max >= 0.0;  // (a NaN t_max fails the compare)
-        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(q.origin[k]) && std::isfinite(q.dir[k]);
-        ok = ok && (q.dir[0] != 0.0 || q.dir[1] != 0.0 || q.dir[2] != 0.0);
-        if (!ok)
-            return set_error(RT_EINVAL, "ray " + std::to_string(i) +
-                                            ": non-finite origin, direction or time, zero direction, or NaN / negative t_max");
-    }
+    if ((rc = check_rays(rays, n)) != RT_OK) return rc;
     char* buf = nullptr;
     const size_t ray_bytes = (size_t)n * sizeof(rt_ray), out_bytes = (size_t)n * query_out_bytes(kind);
     hipError_t e = hipMalloc((void**)&buf, ray_bytes + out_bytes);
@@ -1238,6 +1265,132 @@ int32_t rt_world_occluded_device(rt_scene* s, int32_t world, uint64_t seed, uint
 int32_t rt_world_occluded(rt_scene* s, int32_t world, uint64_t seed, uint32_t flags, const rt_ray* rays, uint64_t n,
                           uint8_t* out) {
     return query_host(s, world, seed, flags, rays, n, Q_OCCLUDED, out);
+}
+
+// ---- rt_world_radiance: Camera::ray_color for caller-given rays
+void rt_radiance_opts_default(rt_radiance_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->struct_size = (uint32_t)sizeof *o;
+    o->max_depth = 10;
+    o->samples = 1;
+    o->background_tex = -1;
+}
+
+// The argument checks of both variants; n == 0 is decided by the caller after them
+static int32_t radiance_args(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* o, const void* rays,
+                             uint64_t n, const void* out) {
+    if (!s) return set_error(RT_EINVAL, "null scene");
+    if (!o) return set_error(RT_EINVAL, "null options");
+    if (o->struct_size < sizeof(rt_radiance_opts))  // this version reads every field below
+        return set_error(RT_EINVAL, "rt_radiance_opts.struct_size is " + std::to_string(o->struct_size) +
+                                        ", this version needs " + std::to_string(sizeof(rt_radiance_opts)) +
+                                        ": initialise the options with rt_radiance_opts_default");
+    if (o->samples == 0) return set_error(RT_EINVAL, "samples must be at least 1");
+    if (o->flags & ~RT_FLAG_REFERENCE_BVH) return set_error(RT_EINVAL, "unknown flags");
+    if (n > (1ull << 32) - o->first_index)
+        return set_error(RT_EINVAL, "first_index + n must not pass 2^32 (a ray's index is its RNG pixel)");
+    const int32_t rc = validate_handles(s, world, lights, o->background_tex);
+    if (rc != RT_OK) return rc;
+    if (n && (!rays || !out)) return set_error(RT_EINVAL, "null ray or output array");
+    return RT_OK;
+}
+
+// Enqueues the query on `stream` of the current device: slot 0's device world
+// as a render of (world, lights, background_tex, flags) leaves it or finds it,
+// after the slot's previous work.  out_dev == NULL (the host variant at
+// max_depth 0): everything but device work on the rays.
+static int32_t radiance_enqueue(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* o,
+                                const rt_ray* rays_dev, uint64_t n, rt_radiance* out_dev, hipStream_t stream) {
+    int cur = -1;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
+    if (!rtk_launch_radiance) return set_error(RT_EUNSUPPORTED, "this build holds no radiance-query kernels");
+    DeviceWorld* d = nullptr;
+    int32_t rc = query_slot(s, d);
+    if (rc != RT_OK) return rc;
+    FlatWorld fw;
+    double flatten_ms = 0;
+    if ((rc = upload_world(s, d, world, lights, o->background_tex, (o->flags & RT_FLAG_REFERENCE_BVH) != 0, fw,
+                           flatten_ms)) != RT_OK)
+        return rc;
+    if (!out_dev) return RT_OK;
+    if ((rc = query_order(s->rs, d, stream)) != RT_OK) return rc;
+    if (o->max_depth == 0) {  // every ray_color returns BLACK (camera.rs:282-284)
+        if ((e = hipMemsetAsync(out_dev, 0, (size_t)n * sizeof(rt_radiance), stream)) != hipSuccess)
+            return hip_fail(e, "hipMemsetAsync radiance");
+    } else {
+        // the kernel's ray counter: a word of the slot's queue buffer (256 B)
+        // that no path kernel reads, on a cache line of its own
+        // RT_RADIANCE_GRID caps the grid (a measurement knob, like the render's
+        // RT_CHUNK_*): with fewer lanes than rays every lane takes its further
+        // rays from the counter, which a small batch otherwise never does
+        const uint32_t grid = std::max(1u, std::min((uint32_t)d->grid[d->tier], env_u32("RT_RADIANCE_GRID", ~0u)));
+        e = rtk_launch_radiance(&d->view, rays_dev, out_dev, n, o->seed, o->first_index, o->samples, o->max_depth,
+                                d->queue + 16, d->tier, (int)grid, d->stack_ovf, stream);
+        if (e != hipSuccess) return hip_fail(e, "radiance kernel launch");
+    }
+    if ((e = hipEventRecord(d->ev_done, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    d->done_recorded = true;
+    return RT_OK;
+}
+
+int32_t rt_world_radiance_device(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* opts,
+                                 const rt_ray* rays_dev, uint64_t n, rt_radiance* out_dev) {
+    const int32_t rc = radiance_args(s, world, lights, opts, rays_dev, n, out_dev);
+    if (rc != RT_OK || n == 0) return rc;
+    try {
+        return radiance_enqueue(s, world, lights, opts, rays_dev, n, out_dev, (hipStream_t)opts->stream);
+    } catch (const std::bad_alloc&) {
+        return set_error(RT_ENOMEM, "out of host memory");
+    }
+}
+
+int32_t rt_world_radiance(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* opts, const rt_ray* rays,
+                          uint64_t n, rt_radiance* out) {
+    int32_t rc = radiance_args(s, world, lights, opts, rays, n, out);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = check_rays(rays, n)) != RT_OK) return rc;
+    if (opts->max_depth == 0) {
+        // no kernel launch and no staging: the world still goes the render's
+        // way (its errors are rt_render's), then the zeros are written here
+        try {
+            rc = radiance_enqueue(s, world, lights, opts, nullptr, n, nullptr, nullptr);
+        } catch (const std::bad_alloc&) {
+            rc = set_error(RT_ENOMEM, "out of host memory");
+        }
+        if (rc == RT_OK) std::memset(out, 0, (size_t)n * sizeof(rt_radiance));
+        return rc;
+    }
+    char* buf = nullptr;
+    const size_t ray_bytes = (size_t)n * sizeof(rt_ray), out_bytes = (size_t)n * sizeof(rt_radiance);
+    hipError_t e = hipMalloc((void**)&buf, ray_bytes + out_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc rays");
+    rt_radiance* out_dev = (rt_radiance*)(buf + ray_bytes);
+    if ((e = hipMemcpy(buf, rays, ray_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        rc = hip_fail(e, "hipMemcpy rays");
+    } else {
+        try {
+            rc = radiance_enqueue(s, world, lights, opts, (const rt_ray*)buf, n, out_dev, nullptr);
+        } catch (const std::bad_alloc&) {
+            rc = set_error(RT_ENOMEM, "out of host memory");
+        }
+        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "query (stream synchronize)");
+        if (rc == RT_OK && (e = hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = hip_fail(e, "hipMemcpy results");
+        if (rc == RT_OK && rtk_check_read) {  // check build: refs past their arrays, as a render reports them
+            unsigned long long c[2] = {0, 0};
+            if ((e = (hipError_t)rtk_check_read(c, 1)) != hipSuccess)
+                rc = hip_fail(e, "check counters");
+            else if (c[0])
+                rc = set_error(RT_EPANIC, "check build: " + std::to_string(c[0]) +
+                                              " decoded ref(s) past their array (first: kind " +
+                                              std::to_string(rtk::ref_kind((uint32_t)c[1])) + ", index " +
+                                              std::to_string(rtk::ref_index((uint32_t)c[1])) + ")");
+        }
+    }
+    (void)hipFree(buf);
+    return rc;
 }
 
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t bg, uint32_t flags, rt_world_info* out) {

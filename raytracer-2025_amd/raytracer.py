@@ -20,12 +20,16 @@ import os
 
 import numpy as np
 
-from .capi import Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtRay, RtRenderOpts, RtStats, d3, d4
+from .capi import (Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtRadiance, RtRadianceOpts, RtRay, RtRenderOpts,
+                   RtStats, d3, d4)
 
 # rt_hit_record as a numpy record (80 B, the C layout)
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
                       ("mat", "<i4"), ("flags", "<u4")])
 assert HIT_DTYPE.itemsize == C.sizeof(RtHitRecord)
+# rt_radiance as a numpy record (32 B, the C layout)
+RADIANCE_DTYPE = np.dtype([("rgb", "<f8", (3,)), ("rays", "<u4"), ("panics", "<u4")])
+assert RADIANCE_DTYPE.itemsize == C.sizeof(RtRadiance)
 
 
 class Texture:
@@ -270,6 +274,44 @@ class Scene:
         self._c(self.api.world_occluded_device(self.s, world.h, int(seed), int(flags), C.c_void_p(int(rays_ptr)),
                                                int(n), C.c_void_p(int(out_ptr)),
                                                C.c_void_p(stream) if stream else None))
+
+    # ---- Camera::ray_color (camera.rs:275-325) for caller-given rays
+    def _radiance_opts(self, max_depth, samples, seed, background, first_index, flags, stream=None):
+        o = RtRadianceOpts()
+        self.api.radiance_opts_default(C.byref(o))
+        o.max_depth, o.samples, o.seed = int(max_depth), int(samples), int(seed)
+        o.background_tex = -1 if background is None else background.h
+        o.first_index, o.flags = int(first_index), int(flags)
+        o.stream = C.c_void_p(stream) if stream else None
+        return o
+
+    def radiance(self, world, lights, rays, *, max_depth=10, samples=1, seed=0, background=None, first_index=0, flags=0):
+        """Camera::ray_color(Ray{origin, dir, time}, max_depth, world, lights)
+        for each row of the (n, 8) float64 array `rays`, as `hit` takes them,
+        `samples` times a ray (rt_world_radiance).  `background` is a Texture
+        (Camera.background) or None for black; t_max bounds the first hit
+        only; the RNG pixel of ray i is first_index + i.  Returns (rgb (n, 3)
+        float64: the mean over the samples, rays (n,) uint32: ray_color calls,
+        panics (n,) uint32: samples that panicked)."""
+        a = np.ascontiguousarray(rays, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) array: origin, direction, time, t_max")
+        n = a.shape[0]
+        out = np.zeros(n, dtype=RADIANCE_DTYPE)
+        o = self._radiance_opts(max_depth, samples, seed, background, first_index, flags)
+        self._c(self.api.world_radiance(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                        a.ctypes.data_as(C.POINTER(RtRay)), n, out.ctypes.data_as(C.POINTER(RtRadiance))))
+        return out["rgb"].copy(), out["rays"].copy(), out["panics"].copy()
+
+    def radiance_device(self, world, lights, rays_ptr, n, out_ptr, *, max_depth=10, samples=1, seed=0, background=None,
+                        first_index=0, flags=0, stream=None):
+        """rt_world_radiance_device: n rt_ray at the device address rays_ptr, n
+        rt_radiance (RADIANCE_DTYPE) written at out_ptr, enqueued on `stream`
+        (a hipStream_t as an integer; None = the default stream) without
+        waiting."""
+        o = self._radiance_opts(max_depth, samples, seed, background, first_index, flags, stream)
+        self._c(self.api.world_radiance_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                               C.c_void_p(int(rays_ptr)), int(n), C.c_void_p(int(out_ptr))))
 
 
 class Camera:
