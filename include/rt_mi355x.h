@@ -417,6 +417,98 @@ int32_t rt_world_radiance(rt_scene* s, int32_t world, int32_t lights, const rt_r
 int32_t rt_world_radiance_device(rt_scene* s, int32_t world, int32_t lights, const rt_radiance_opts* opts,
                                  const rt_ray* rays_device, uint64_t n, rt_radiance* out_device);
 
+/* ---- Lights queries: Hittable::pdf_value and Hittable::random of the lights ---- */
+/* The two Hittable methods (hit.rs:46-60) the reference's importance sampling
+ * rests on, called through HittablePDF (pdf.rs:66-88) on the lights object at
+ * every diffuse vertex (camera.rs:298-311), open to any batch of points: a
+ * next-event-estimation vertex of a host-side integrator built on rt_world_hit
+ * and rt_world_occluded, a light probe, a lightmap texel, a many-light study. */
+typedef struct rt_lights_opts {
+    uint32_t struct_size;   /* set by rt_lights_opts_default; fields only ever appended */
+    uint32_t flags;         /* RT_FLAG_REFERENCE_BVH or 0 */
+    uint64_t seed;          /* RNG key (rt_lights_sample only) */
+    uint32_t samples;       /* rt_lights_sample: draws per origin, >= 1; rt_lights_pdf ignores it */
+    uint32_t first_index;   /* RNG pixel of origin 0; origin i uses first_index + i */
+    int32_t background_tex; /* only selects the flattening, see below; -1 = BLACK */
+    uint32_t reserved;
+    void* stream;           /* device variants only; NULL = default stream */
+    uint64_t reserved1;     /* room for a later version's field; not read */
+} rt_lights_opts;           /* 48 B */
+/* samples 1, background_tex -1, everything else 0 */
+void rt_lights_opts_default(rt_lights_opts* opts);
+
+typedef struct rt_light_sample {
+    double dir[3];   /* lights.random(origin): a unit vector */
+    double pdf;      /* lights.pdf_value(origin, dir): HittablePDF::value of that draw */
+    uint32_t flags;  /* RT_LIGHT_PANIC */
+    uint32_t reserved;
+} rt_light_sample;   /* 40 B */
+#define RT_LIGHT_PANIC 1u
+
+/* rt_lights_pdf: out[i] = lights.pdf_value(origin_i, dir_i) for i < n; origins3
+ * and dirs3 are n packed triples of doubles.  Quad::pdf_value quad.rs:108-120
+ * (Triangle likewise), Sphere::pdf_value sphere.rs:114-132, Hittables::pdf_value
+ * hits.rs:52-67 (the children's values summed in order, over their count),
+ * Transform::pdf_value shapes.rs:117-123.  The direction is used as given (not
+ * normalised).  The reference makes the ray with Ray::new at time 0
+ * (ray.rs:11-17), so a moving sphere is taken at center.at(0); the interval
+ * tested is [1e-8, inf).  The value is returned as computed: a direction that
+ * misses every light gives 0, and where the arithmetic gives NaN, NaN is
+ * returned -- there Hittables::pdf_value panics with "The sum of pdf is NaN!"
+ * (hits.rs:52-67) and ray_color's own check panics (camera.rs:323);
+ * pdf_value has no other panic.
+ *
+ * rt_lights_sample: out[i * samples + s] is draw s for origin i:
+ * dir = lights.random(origin_i) (Hittables::random hits.rs:69-75,
+ * Quad quad.rs:122-125, Triangle triangle.rs:117-128, Sphere sphere.rs:134-144,
+ * Transform shapes.rs:125-132) and pdf = lights.pdf_value(origin_i, dir).
+ * RNG: the contract's main stream (oracle/rng_contract.hpp) keyed (seed,
+ * pixel = first_index + i, sample = s, vertex = 1), slots 0, 1, 2, ... in the
+ * order random draws them: a list's child choice first at each list level,
+ * then the primitive's two (the deepest accepted tree draws 6, under the
+ * contract's 16).  A draw panics when one of random's expects fails -- a
+ * direction that cannot be normalised, as from an origin at a sphere light's
+ * centre: such a draw has flags = RT_LIGHT_PANIC, dir = 0 and pdf = 0.  A NaN
+ * pdf on a good direction is returned as NaN without the flag, as in
+ * rt_lights_pdf.  A result depends on (seed, first_index + i, s) alone, never
+ * on scheduling or on the batch's size.
+ *
+ * world, lights, flags and background_tex name the flattening: the world is
+ * flattened and uploaded exactly as for rt_render(world, lights,
+ * background_tex, flags) and shares the scene's per-device world cache, so a
+ * render, a radiance query and a lights query of one flattening upload once.
+ * lights.pdf_value does not need the world; it is an argument because the
+ * cache holds one flattening per scene and device, and a lights-only
+ * flattening would evict a million-triangle world between a hit query and the
+ * light sample that follows it.  Every lights object rt_render accepts is
+ * accepted and every one it refuses is refused with rt_render's code and
+ * message (a BVH or a ConstantMedium among the lights, or an empty list:
+ * RT_EPANIC; a tree deeper than 4 levels: RT_EUNSUPPORTED).  lights = -1 is
+ * RT_EINVAL: `lights: None` has nothing to sample.
+ *
+ * RT_EINVAL: a null scene or opts; struct_size below this version's;
+ * samples == 0 (rt_lights_sample); unknown flags; first_index + n > 2^32;
+ * n * samples >= 2^40; a null array with n > 0; in the host variants a
+ * non-finite origin or (rt_lights_pdf) a non-finite or zero direction, named
+ * in rt_last_error by its index as rt_world_hit names a ray.  RT_EHANDLE /
+ * RT_EMOVED as rt_render gives them.  RT_EDEVICE without a gfx950 device
+ * (there is no CPU fallback).  n == 0 is RT_OK, touches no device and needs
+ * no arrays.  The device work is ordered after the scene's previous device
+ * work, as the other queries' is.  Host arrays, on the calling thread's
+ * current device, blocking: */
+int32_t rt_lights_pdf(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, const double* origins3,
+                      const double* dirs3, uint64_t n, double* out);
+int32_t rt_lights_sample(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, const double* origins3,
+                         uint64_t n, rt_light_sample* out);
+/* The same from and to gfx950 device arrays, enqueued on opts->stream without
+ * waiting.  The arrays are the caller's duty, as in rt_world_hit_device; the
+ * kernel ends and writes an output for any input, and none past out_device[n - 1]
+ * (rt_lights_sample_device: out_device[n * samples - 1]). */
+int32_t rt_lights_pdf_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts,
+                             const double* origins3_device, const double* dirs3_device, uint64_t n, double* out_device);
+int32_t rt_lights_sample_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts,
+                                const double* origins3_device, uint64_t n, rt_light_sample* out_device);
+
 /* Number of rows a shard renders (rows of the compact output). */
 uint32_t rt_shard_rows(const rt_camera* cam, const rt_render_opts* opts);
 

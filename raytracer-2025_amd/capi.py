@@ -134,6 +134,35 @@ class RtRadiance(C.Structure):
     ]
 
 
+class RtLightsOpts(C.Structure):
+    """rt_lights_opts -- the options of rt_lights_pdf / rt_lights_sample (made by rt_lights_opts_default)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("samples", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("background_tex", C.c_int32),
+        ("reserved", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("reserved1", C.c_uint64),
+    ]
+
+
+class RtLightSample(C.Structure):
+    """rt_light_sample -- one draw of rt_lights_sample (40 B)."""
+
+    _fields_ = [
+        ("dir", c_double3),
+        ("pdf", C.c_double),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+LIGHT_PANIC = 1
+
 _P = C.c_void_p
 _I = C.c_int32
 _U = C.c_uint32
@@ -190,6 +219,13 @@ SIGNATURES = {
     "world_radiance": (_I, [_P, _I, _I, C.POINTER(RtRadianceOpts), C.POINTER(RtRay), C.c_uint64,
                             C.POINTER(RtRadiance)]),
     "world_radiance_device": (_I, [_P, _I, _I, C.POINTER(RtRadianceOpts), _P, C.c_uint64, _P]),
+    "lights_opts_default": (None, [C.POINTER(RtLightsOpts)]),
+    "lights_pdf": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64,
+                        C.POINTER(C.c_double)]),
+    "lights_pdf_device": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), _P, _P, C.c_uint64, _P]),
+    "lights_sample": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), C.POINTER(C.c_double), C.c_uint64,
+                           C.POINTER(RtLightSample)]),
+    "lights_sample_device": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), _P, C.c_uint64, _P]),
     "shard_rows": (_U, [C.POINTER(RtCamera), C.POINTER(RtRenderOpts)]),
     "render_device": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), _P]),
     "render_device_wait": (_I, [_P, C.POINTER(RtStats)]),
@@ -212,7 +248,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "lights_opts_default", "lights_pdf", "lights_pdf_device", "lights_sample", "lights_sample_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -1,6 +1,7 @@
 // rt_kernel.h -- interface between the host render driver (rt_render.cpp) and
 // the gfx950 kernels (rt_kernel_path.hip, rt_kernel_hit.hip,
-// rt_kernel_occl.hip, rt_kernel_radiance.hip, rt_kernel_common.hip).
+// rt_kernel_occl.hip, rt_kernel_radiance.hip, rt_kernel_lights.hip,
+// rt_kernel_common.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -181,6 +182,20 @@ extern "C" __attribute__((weak)) hipError_t rtk_launch_radiance(const rtk::Scene
                                                                 uint32_t first_index, uint32_t samples,
                                                                 uint32_t max_depth, uint32_t* counter, int tier, int grid,
                                                                 void* stack_ovf, hipStream_t stream);
+// rt_lights_pdf's and rt_lights_sample's kernels: lights.pdf_value of n
+// (origin, direction) pairs, and `samples` draws of lights.random an origin
+// with their pdf_value (device arrays; the Rng pixel of origin i is
+// first_index + i).  They read view->lights_root and walk no world, so there is
+// no tier and no stack: at most `grid` blocks of RT_BLOCK.  Weak as
+// rtk_launch_hits is.
+struct rt_light_sample;
+extern "C" __attribute__((weak)) hipError_t rtk_launch_lights_pdf(const rtk::SceneView* view, const double* origins3,
+                                                                  const double* dirs3, double* out, uint64_t n, int grid,
+                                                                  hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t rtk_launch_lights_sample(const rtk::SceneView* view, const double* origins3,
+                                                                     struct rt_light_sample* out, uint64_t n,
+                                                                     uint64_t seed, uint32_t first_index, uint32_t samples,
+                                                                     int grid, hipStream_t stream);
 // The Disney self-test (rt_disney_selftest): fn's doubles per case in and out
 // (0 for an unknown fn), and n cases of the BSDF's device functions as the
 // path kernel's Disney tier compiles them.  Weak as rtk_launch_hits is: absent

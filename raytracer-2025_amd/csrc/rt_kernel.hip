@@ -31,10 +31,11 @@
 // beside the headers the CPU tests compile too (rt_slab.h, rt_sort4.h, ...).
 //
 // This file is the whole build (the check library, whose kernels share one
-// g_check, and the A/B libraries): the five units.  The product library
+// g_check, and the A/B libraries): the six units.  The product library
 // compiles each as an object of its own, the path kernel's once per tier.
 #include "rt_kernel_path.hip"
 #include "rt_kernel_hit.hip"
 #include "rt_kernel_occl.hip"
 #include "rt_kernel_radiance.hip"
+#include "rt_kernel_lights.hip"
 #include "rt_kernel_common.hip"

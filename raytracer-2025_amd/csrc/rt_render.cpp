@@ -1393,6 +1393,164 @@ int32_t rt_world_radiance(rt_scene* s, int32_t world, int32_t lights, const rt_r
     return rc;
 }
 
+// ---- rt_lights_pdf / rt_lights_sample: Hittable::pdf_value and ::random of the lights
+void rt_lights_opts_default(rt_lights_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->struct_size = (uint32_t)sizeof *o;
+    o->samples = 1;
+    o->background_tex = -1;
+}
+
+// Which of the two a call is, and with it what it reads and writes an item
+enum LightsKind { L_PDF, L_SAMPLE };
+
+// The argument checks of the four variants; n == 0 is decided by the caller
+// after them.  dirs: the pdf query's second input (not looked at otherwise).
+static int32_t lights_args(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* o, LightsKind kind,
+                           const void* origins, const void* dirs, uint64_t n, const void* out) {
+    if (!s) return set_error(RT_EINVAL, "null scene");
+    if (!o) return set_error(RT_EINVAL, "null options");
+    if (o->struct_size < sizeof(rt_lights_opts))  // this version reads every field below
+        return set_error(RT_EINVAL, "rt_lights_opts.struct_size is " + std::to_string(o->struct_size) +
+                                        ", this version needs " + std::to_string(sizeof(rt_lights_opts)) +
+                                        ": initialise the options with rt_lights_opts_default");
+    if (kind == L_SAMPLE && o->samples == 0) return set_error(RT_EINVAL, "samples must be at least 1");
+    if (o->flags & ~RT_FLAG_REFERENCE_BVH) return set_error(RT_EINVAL, "unknown flags");
+    if (n > (1ull << 32) - o->first_index)
+        return set_error(RT_EINVAL, "first_index + n must not pass 2^32 (an origin's index is its RNG pixel)");
+    // (n <= 2^32 and samples < 2^32: the product does not wrap)
+    if (kind == L_SAMPLE && n * (uint64_t)o->samples >= (1ull << 40))
+        return set_error(RT_EINVAL, "n * samples must be below 2^40");
+    if (lights == -1) return set_error(RT_EINVAL, "lights: None has nothing to sample (lights = -1)");
+    int32_t rc = validate_handles(s, world, lights, o->background_tex);
+    if (rc != RT_OK) return rc;
+    // what rt_render says of the lights object, before a device is touched
+    if ((rc = lights_check(s, lights)) != RT_OK) return rc;
+    if (n && (!origins || !out || (kind == L_PDF && !dirs))) return set_error(RT_EINVAL, "null input or output array");
+    return RT_OK;
+}
+
+// The host variants' checks of n packed triples: the first bad one by its index
+static int32_t check_triples(const double* a, uint64_t n, bool nonzero, const char* what) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* v = a + 3 * i;
+        bool ok = std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+        if (nonzero) ok = ok && (v[0] != 0.0 || v[1] != 0.0 || v[2] != 0.0);
+        if (!ok)
+            return set_error(RT_EINVAL, std::string(what) + " " + std::to_string(i) +
+                                            (nonzero ? ": non-finite or zero" : ": non-finite"));
+    }
+    return RT_OK;
+}
+
+// Enqueues the query on `stream` of the current device: slot 0's device world
+// as a render of (world, lights, background_tex, flags) leaves it or finds it
+// (not for_query: the render's flattening), after the slot's previous work.
+static int32_t lights_enqueue(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* o, LightsKind kind,
+                              const double* origins_dev, const double* dirs_dev, uint64_t n, void* out_dev,
+                              hipStream_t stream) {
+    int cur = -1;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
+    if (!rtk_launch_lights_pdf || !rtk_launch_lights_sample)
+        return set_error(RT_EUNSUPPORTED, "this build holds no lights-query kernels");
+    DeviceWorld* d = nullptr;
+    int32_t rc = query_slot(s, d);
+    if (rc != RT_OK) return rc;
+    FlatWorld fw;
+    double flatten_ms = 0;
+    if ((rc = upload_world(s, d, world, lights, o->background_tex, (o->flags & RT_FLAG_REFERENCE_BVH) != 0, fw,
+                           flatten_ms)) != RT_OK)
+        return rc;
+    if ((rc = query_order(s->rs, d, stream)) != RT_OK) return rc;
+    // RT_LIGHTS_GRID caps the grid (a measurement and test knob, like
+    // RT_RADIANCE_GRID): with fewer lanes than items every lane makes several
+    // grid-stride trips, which a small batch otherwise never does
+    const uint32_t grid = std::max(1u, std::min((uint32_t)d->grid[d->tier], env_u32("RT_LIGHTS_GRID", ~0u)));
+    e = kind == L_PDF ? rtk_launch_lights_pdf(&d->view, origins_dev, dirs_dev, (double*)out_dev, n, (int)grid, stream)
+                      : rtk_launch_lights_sample(&d->view, origins_dev, (rt_light_sample*)out_dev, n, o->seed,
+                                                 o->first_index, o->samples, (int)grid, stream);
+    if (e != hipSuccess) return hip_fail(e, "lights kernel launch");
+    if ((e = hipEventRecord(d->ev_done, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    d->done_recorded = true;
+    return RT_OK;
+}
+
+static int32_t lights_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, LightsKind kind,
+                             const double* origins_dev, const double* dirs_dev, uint64_t n, void* out_dev) {
+    const int32_t rc = lights_args(s, world, lights, opts, kind, origins_dev, dirs_dev, n, out_dev);
+    if (rc != RT_OK || n == 0) return rc;
+    try {
+        return lights_enqueue(s, world, lights, opts, kind, origins_dev, dirs_dev, n, out_dev, (hipStream_t)opts->stream);
+    } catch (const std::bad_alloc&) {
+        return set_error(RT_ENOMEM, "out of host memory");
+    }
+}
+
+// The host variants: one allocation for inputs and outputs, copied in, queried
+// on the default stream, copied out
+static int32_t lights_host(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, LightsKind kind,
+                           const double* origins, const double* dirs, uint64_t n, void* out) {
+    int32_t rc = lights_args(s, world, lights, opts, kind, origins, dirs, n, out);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = check_triples(origins, n, false, "origin")) != RT_OK) return rc;
+    if (kind == L_PDF && (rc = check_triples(dirs, n, true, "direction")) != RT_OK) return rc;
+    char* buf = nullptr;
+    const size_t tri_bytes = (size_t)n * 3 * sizeof(double);
+    const size_t in_bytes = kind == L_PDF ? 2 * tri_bytes : tri_bytes;
+    const size_t out_bytes = kind == L_PDF ? (size_t)n * sizeof(double) : (size_t)n * opts->samples * sizeof(rt_light_sample);
+    hipError_t e = hipMalloc((void**)&buf, in_bytes + out_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc lights query");
+    const double* dirs_dev = kind == L_PDF ? (const double*)(buf + tri_bytes) : nullptr;
+    void* out_dev = buf + in_bytes;
+    if ((e = hipMemcpy(buf, origins, tri_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (kind == L_PDF && (e = hipMemcpy(buf + tri_bytes, dirs, tri_bytes, hipMemcpyHostToDevice)) != hipSuccess)) {
+        rc = hip_fail(e, "hipMemcpy lights query");
+    } else {
+        try {
+            rc = lights_enqueue(s, world, lights, opts, kind, (const double*)buf, dirs_dev, n, out_dev, nullptr);
+        } catch (const std::bad_alloc&) {
+            rc = set_error(RT_ENOMEM, "out of host memory");
+        }
+        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "query (stream synchronize)");
+        if (rc == RT_OK && (e = hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = hip_fail(e, "hipMemcpy results");
+        if (rc == RT_OK && rtk_check_read) {  // check build: refs past their arrays, as a render reports them
+            unsigned long long c[2] = {0, 0};
+            if ((e = (hipError_t)rtk_check_read(c, 1)) != hipSuccess)
+                rc = hip_fail(e, "check counters");
+            else if (c[0])
+                rc = set_error(RT_EPANIC, "check build: " + std::to_string(c[0]) +
+                                              " decoded ref(s) past their array (first: kind " +
+                                              std::to_string(rtk::ref_kind((uint32_t)c[1])) + ", index " +
+                                              std::to_string(rtk::ref_index((uint32_t)c[1])) + ")");
+        }
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int32_t rt_lights_pdf(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, const double* origins3,
+                      const double* dirs3, uint64_t n, double* out) {
+    return lights_host(s, world, lights, opts, L_PDF, origins3, dirs3, n, out);
+}
+
+int32_t rt_lights_pdf_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts,
+                             const double* origins3_dev, const double* dirs3_dev, uint64_t n, double* out_dev) {
+    return lights_device(s, world, lights, opts, L_PDF, origins3_dev, dirs3_dev, n, out_dev);
+}
+
+int32_t rt_lights_sample(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts, const double* origins3,
+                         uint64_t n, rt_light_sample* out) {
+    return lights_host(s, world, lights, opts, L_SAMPLE, origins3, nullptr, n, out);
+}
+
+int32_t rt_lights_sample_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts,
+                                const double* origins3_dev, uint64_t n, rt_light_sample* out_dev) {
+    return lights_device(s, world, lights, opts, L_SAMPLE, origins3_dev, nullptr, n, out_dev);
+}
+
 int32_t rt_world_info_get(rt_scene* s, int32_t world, int32_t lights, int32_t bg, uint32_t flags, rt_world_info* out) {
     if (!s || !out) return set_error(RT_EINVAL, "null argument");
     if (world < 0 || (size_t)world >= s->objs.size() || s->objs[world].hidden)

@@ -921,6 +921,12 @@ static int tex_needs_uv(const rt_scene* s, int t, int depth = 0) {
     return 0;
 }
 
+int32_t lights_check(const rt_scene* s, int32_t lights) {
+    std::string lerr;
+    const int lk = light_tree(s, lights, 0, lerr);
+    return lk < 0 ? set_error(lk, lerr) : RT_OK;
+}
+
 int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, bool reference_bvh,
                 HostWorld& out) {
     out = HostWorld();

@@ -164,6 +164,11 @@ int32_t set_error(int32_t code, const std::string& msg);
 // the SAH rebuild (closest-hit results agree up to exact t ties).
 int32_t flatten(const rt_scene* s, int32_t world, int32_t lights, int32_t background_tex, bool reference_bvh,
                 HostWorld& out);
+// What flatten says of `lights` (a valid object handle) as a lights object,
+// before anything else of the world is looked at: RT_OK, or flatten's code
+// with its message set (a BVH, a ConstantMedium or an empty list: RT_EPANIC;
+// a tree deeper than 4 levels: RT_EUNSUPPORTED).
+int32_t lights_check(const rt_scene* s, int32_t lights);
 // Collapses every two-box BVH into 4-wide nodes (hw.nodes4; sphere children with
 // their own padded box, queued not stacked, when filter_spheres: the basic
 // tier), rewrites the K_BVH refs

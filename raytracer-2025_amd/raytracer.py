@@ -20,8 +20,8 @@ import os
 
 import numpy as np
 
-from .capi import (Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtRadiance, RtRadianceOpts, RtRay, RtRenderOpts,
-                   RtStats, d3, d4)
+from .capi import (Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtLightSample, RtLightsOpts, RtRadiance,
+                   RtRadianceOpts, RtRay, RtRenderOpts, RtStats, d3, d4)
 
 # rt_hit_record as a numpy record (80 B, the C layout)
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
@@ -30,6 +30,9 @@ assert HIT_DTYPE.itemsize == C.sizeof(RtHitRecord)
 # rt_radiance as a numpy record (32 B, the C layout)
 RADIANCE_DTYPE = np.dtype([("rgb", "<f8", (3,)), ("rays", "<u4"), ("panics", "<u4")])
 assert RADIANCE_DTYPE.itemsize == C.sizeof(RtRadiance)
+# rt_light_sample as a numpy record (40 B, the C layout)
+LIGHT_SAMPLE_DTYPE = np.dtype([("dir", "<f8", (3,)), ("pdf", "<f8"), ("flags", "<u4"), ("reserved", "<u4")])
+assert LIGHT_SAMPLE_DTYPE.itemsize == C.sizeof(RtLightSample)
 
 
 class Texture:
@@ -312,6 +315,70 @@ class Scene:
         o = self._radiance_opts(max_depth, samples, seed, background, first_index, flags, stream)
         self._c(self.api.world_radiance_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
                                                C.c_void_p(int(rays_ptr)), int(n), C.c_void_p(int(out_ptr))))
+
+    # ---- Hittable::pdf_value / ::random of the lights (hit.rs:46-60, pdf.rs:66-88)
+    def _lights_opts(self, samples=1, seed=0, first_index=0, background=None, flags=0, stream=None):
+        o = RtLightsOpts()
+        self.api.lights_opts_default(C.byref(o))
+        o.samples, o.seed, o.first_index, o.flags = int(samples), int(seed), int(first_index), int(flags)
+        o.background_tex = -1 if background is None else background.h
+        o.stream = C.c_void_p(stream) if stream else None
+        return o
+
+    @staticmethod
+    def _triples(a, name):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must be an (n, 3) array")
+        return a
+
+    def lights_pdf(self, world, lights, origins, dirs, **opts):
+        """lights.pdf_value(origin, dir) for each row of the (n, 3) float64
+        arrays `origins` and `dirs` (rt_lights_pdf); the directions are used as
+        given.  `world`, `background` (a Texture or None) and `flags` name the
+        flattening, as for a render.  Returns an (n,) float64 array."""
+        o_, d_ = self._triples(origins, "origins"), self._triples(dirs, "dirs")
+        if o_.shape != d_.shape:
+            raise ValueError("origins and dirs must have the same shape")
+        n = o_.shape[0]
+        out = np.zeros(n, dtype=np.float64)
+        o = self._lights_opts(**opts)
+        dp = C.POINTER(C.c_double)
+        self._c(self.api.lights_pdf(self.s, world.h, -1 if lights is None else lights.h, C.byref(o), o_.ctypes.data_as(dp),
+                                    d_.ctypes.data_as(dp), n, out.ctypes.data_as(dp)))
+        return out
+
+    def lights_sample(self, world, lights, origins, samples=1, seed=0, first_index=0, **opts):
+        """`samples` draws of lights.random(origin) for each row of the (n, 3)
+        float64 array `origins`, each with its lights.pdf_value
+        (rt_lights_sample); the RNG pixel of origin i is first_index + i.
+        Returns an (n, samples) array of LIGHT_SAMPLE_DTYPE: dir, pdf, flags
+        (capi.LIGHT_PANIC: random panicked, dir and pdf are zero)."""
+        o_ = self._triples(origins, "origins")
+        n = o_.shape[0]
+        out = np.zeros((n, max(int(samples), 0)), dtype=LIGHT_SAMPLE_DTYPE)
+        o = self._lights_opts(samples, seed, first_index, **opts)
+        self._c(self.api.lights_sample(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                       o_.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                       out.ctypes.data_as(C.POINTER(RtLightSample))))
+        return out
+
+    def lights_pdf_device(self, world, lights, origins_ptr, dirs_ptr, n, out_ptr, **opts):
+        """rt_lights_pdf_device: n packed triples of doubles at each of the
+        device addresses origins_ptr and dirs_ptr, n doubles written at out_ptr,
+        enqueued on `stream` (a hipStream_t as an integer; None = the default
+        stream) without waiting."""
+        o = self._lights_opts(**opts)
+        self._c(self.api.lights_pdf_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                           C.c_void_p(int(origins_ptr)), C.c_void_p(int(dirs_ptr)), int(n),
+                                           C.c_void_p(int(out_ptr))))
+
+    def lights_sample_device(self, world, lights, origins_ptr, n, out_ptr, samples=1, seed=0, first_index=0, **opts):
+        """rt_lights_sample_device: n packed triples at origins_ptr, n * samples
+        rt_light_sample (LIGHT_SAMPLE_DTYPE) written at out_ptr, likewise."""
+        o = self._lights_opts(samples, seed, first_index, **opts)
+        self._c(self.api.lights_sample_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                              C.c_void_p(int(origins_ptr)), int(n), C.c_void_p(int(out_ptr))))
 
 
 class Camera:
