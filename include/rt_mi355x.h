@@ -509,6 +509,113 @@ int32_t rt_lights_pdf_device(rt_scene* s, int32_t world, int32_t lights, const r
 int32_t rt_lights_sample_device(rt_scene* s, int32_t world, int32_t lights, const rt_lights_opts* opts,
                                 const double* origins3_device, uint64_t n, rt_light_sample* out_device);
 
+/* ---- Scatter queries: Material::emitted / ::scatter and the PDF behind it ----- */
+/* One ray_color level (camera.rs:286-316) for caller-given rays, without the
+ * recursion and without the lights mix: what the surface a ray meets emits,
+ * how it scatters, and the BSDF and density of a direction the caller drew
+ * elsewhere (towards a light: rt_lights_sample).  With rt_lights_* and
+ * rt_world_occluded the caller owns the integrator's loop -- next-event
+ * estimation, MIS, Russian roulette, path guiding, first-hit AOVs -- while
+ * every bounce runs on the library's walk and its materials: textures, Mix /
+ * DiffuseLight wrappers, OBJ RemappedMaterials, Disney and Portal included.
+ * The query takes rays, not hit records: an OBJ triangle's material needs the
+ * primitive (remap_record, obj.rs:32-62), and no caller-given index is read. */
+typedef struct rt_scatter_opts {
+    uint32_t struct_size;   /* set by rt_scatter_opts_default; fields only ever appended */
+    uint32_t flags;         /* RT_FLAG_REFERENCE_BVH or 0 */
+    uint64_t seed;          /* RNG key (oracle/rng_contract.hpp) */
+    uint32_t sample;        /* RNG sample coordinate of every ray of the call */
+    uint32_t vertex;        /* RNG vertex coordinate, 1 <= vertex < 2^28: the k-th ray_color call of the caller's path */
+    uint32_t first_index;   /* RNG pixel of ray i is first_index + i when `indices` is NULL */
+    int32_t background_tex; /* Camera.background: what a miss returns; -1 = BLACK */
+    void* stream;           /* device variant only; NULL = default stream */
+    uint64_t reserved1;     /* not read */
+} rt_scatter_opts;          /* 48 B */
+/* vertex 1, background_tex -1, everything else 0 */
+void rt_scatter_opts_default(rt_scatter_opts* opts);
+
+typedef struct rt_scatter {
+    rt_hit_record hit;  /* exactly rt_world_hit's record for this ray (before remap_record) */
+    double emitted[3];  /* hit: rec.mat.emitted(r, rec); miss: Environment::value(r) */
+    double f[3];        /* RT_SCATTER_RAY: the attenuation; RT_SCATTER_PDF: PDF::value(dir).0 */
+    double pdf;         /* RT_SCATTER_PDF: PDF::value(dir).1 (may be 0: camera.rs:309 is the caller's assert); else 0 */
+    double origin[3];   /* the scattered ray's origin (rec.p; Portal: rec.p + offset) */
+    double dir[3];      /* RAY: skip_pdf_ray's direction as made (not normalised); PDF: PDF::generate() */
+    double eval_f[3];   /* RT_SCATTER_EVAL: PDF::value(eval_dir).0 */
+    double eval_pdf;    /* RT_SCATTER_EVAL: PDF::value(eval_dir).1 */
+    uint32_t flags;     /* RT_SCATTER_* */
+    uint32_t draws;     /* main-stream slots of this vertex the reference's code consumed */
+} rt_scatter;           /* 224 B */
+#define RT_SCATTER_RAY 1u       /* scatter returned ScatterRecord::Ray */
+#define RT_SCATTER_PDF 2u       /* scatter returned ScatterRecord::PDF */
+#define RT_SCATTER_NO_SAMPLE 4u /* with PDF: generate() returned None (Disney); dir, f, pdf are 0 */
+#define RT_SCATTER_EVAL 8u      /* eval_f / eval_pdf hold PDF::value(eval_dir) */
+#define RT_SCATTER_PANIC 16u    /* a reference unwrap / expect / assert of this level failed */
+
+/* For ray i of n: world.hit(Ray{origin, dir, time}, [1e-8, t_max]) -- t_max is
+ * the first-hit bound as in rt_world_radiance: a hit past it is a miss -- and
+ * `hit` is bit for bit what rt_world_hit writes for that ray (its query-mode
+ * (u, v) and mat, RT_HIT_MEDIUM and the medium's normal included).
+ * A miss: `hit` is the miss record, emitted = Environment::value of
+ * background_tex (black for -1), every other field 0, flags 0.
+ * A hit: the shading record is the path kernels' -- remap_record with vertex
+ * normals, texture coordinates and normal map for an OBJ triangle.  emitted =
+ * Material::emitted through the wrapper tree (DiffuseLight, Mix), returned as
+ * computed: a NaN is a NaN (the check of camera.rs:323 is ray_color's).  Then
+ * Material::scatter through the wrappers, the Mix draws first:
+ *   None (a light, Metal's `?`, a DiffuseLight without a material): neither
+ *     kind bit; f, pdf, origin and dir are 0.
+ *   ScatterRecord::Ray (Metal, Dielectric, Transparent, Portal):
+ *     RT_SCATTER_RAY; f the attenuation, (origin, dir) the ray, pdf 0.
+ *   ScatterRecord::PDF (CosinePDF, SpherePDF, DisneyPDF): RT_SCATTER_PDF;
+ *     dir = generate(), (f, pdf) = value(dir), origin = rec.p.  A generate()
+ *     that returns None (Disney) adds RT_SCATTER_NO_SAMPLE and leaves them 0.
+ * There is no lights mix: no MixturePDF and no mixture draw.  The slots of the
+ * vertex are the wrappers' draws, then the material's, then generate's, in
+ * reference order, and `draws` counts them; the caller mixes with the lights
+ * itself through rt_lights_*.  The scattered ray's time is the ray's own.
+ * eval_dirs3, when not NULL, holds n packed triples: for an RT_SCATTER_PDF
+ * record (eval_f, eval_pdf) = PDF::value(eval_dir_i) of the same PDF object --
+ * the BSDF half of an MIS weight for a direction drawn from the lights -- and
+ * RT_SCATTER_EVAL is set, whether or not generate() returned a direction; for
+ * every other outcome the two fields are 0 and the bit is clear.
+ * A panic of the level (remap_record's unwraps, unit() of the incoming
+ * direction in Dielectric, the ONB / CosinePDF::value unwraps, Disney's panics,
+ * more than 16 slots): flags == RT_SCATTER_PANIC alone, `hit` stays, every
+ * other field 0.  pdf == 0 is not a panic here.
+ * RNG: the contract's main and medium streams (oracle/rng_contract.hpp) keyed
+ * (seed, pixel, sample, vertex) with pixel = indices[i], or first_index + i
+ * when indices is NULL: a caller that compacts its live paths between bounces
+ * keeps each path's stream by handing its pixel on.  A result depends on that
+ * key, the ray and its eval direction alone, never on n or on scheduling.  So
+ * in a world rendered without lights the query applied at vertex 1, 2, ...
+ * with stable indices retraces the path rt_render / rt_world_radiance trace,
+ * draw for draw, media included.
+ * The world is flattened and uploaded as for rt_render(world, lights,
+ * background_tex, flags) and shares the scene's per-device world cache;
+ * `lights` only names the flattening (it may be -1) and is never sampled.  The
+ * device work is ordered after the scene's previous device work, as
+ * rt_world_radiance's is.
+ * RT_EINVAL: a null scene or opts; struct_size below this version's; unknown
+ * flags; a vertex outside [1, 2^28); first_index + n > 2^32 with indices NULL;
+ * n >= 2^32; a null rays or out with n > 0; in the host variant a bad ray,
+ * named in rt_last_error as rt_world_hit names it, or a non-finite or zero
+ * eval direction, named by its index.  RT_EHANDLE / RT_EMOVED /
+ * RT_EUNSUPPORTED / RT_ESTACK as rt_render gives them.  RT_EDEVICE without a
+ * gfx950 device (there is no CPU fallback).  n == 0 is RT_OK, touches no
+ * device and needs no arrays.  Host arrays, on the calling thread's current
+ * device, blocking: */
+int32_t rt_world_scatter(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* opts, const rt_ray* rays,
+                         const double* eval_dirs3, const uint32_t* indices, uint64_t n, rt_scatter* out);
+/* The same from and to gfx950 device arrays, enqueued on opts->stream without
+ * waiting.  The arrays are the caller's duty, as in rt_world_hit_device; the
+ * kernel ends and writes a record for any ray, and none past out_device[n - 1].
+ * out_device must be 16-B aligned (RT_EINVAL otherwise): a record is written
+ * as fourteen 16-B stores. */
+int32_t rt_world_scatter_device(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* opts,
+                                const rt_ray* rays_device, const double* eval_dirs3_device,
+                                const uint32_t* indices_device, uint64_t n, rt_scatter* out_device);
+
 /* Number of rows a shard renders (rows of the compact output). */
 uint32_t rt_shard_rows(const rt_camera* cam, const rt_render_opts* opts);
 

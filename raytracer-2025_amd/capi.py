@@ -163,6 +163,42 @@ class RtLightSample(C.Structure):
 
 LIGHT_PANIC = 1
 
+
+class RtScatterOpts(C.Structure):
+    """rt_scatter_opts -- the options of rt_world_scatter (made by rt_scatter_opts_default)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("sample", C.c_uint32),
+        ("vertex", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("background_tex", C.c_int32),
+        ("stream", C.c_void_p),
+        ("reserved1", C.c_uint64),
+    ]
+
+
+class RtScatter(C.Structure):
+    """rt_scatter -- one ray_color level of one query ray of rt_world_scatter (224 B)."""
+
+    _fields_ = [
+        ("hit", RtHitRecord),
+        ("emitted", c_double3),
+        ("f", c_double3),
+        ("pdf", C.c_double),
+        ("origin", c_double3),
+        ("dir", c_double3),
+        ("eval_f", c_double3),
+        ("eval_pdf", C.c_double),
+        ("flags", C.c_uint32),
+        ("draws", C.c_uint32),
+    ]
+
+
+SCATTER_RAY, SCATTER_PDF, SCATTER_NO_SAMPLE, SCATTER_EVAL, SCATTER_PANIC = 1, 2, 4, 8, 16
+
 _P = C.c_void_p
 _I = C.c_int32
 _U = C.c_uint32
@@ -226,6 +262,10 @@ SIGNATURES = {
     "lights_sample": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), C.POINTER(C.c_double), C.c_uint64,
                            C.POINTER(RtLightSample)]),
     "lights_sample_device": (_I, [_P, _I, _I, C.POINTER(RtLightsOpts), _P, C.c_uint64, _P]),
+    "scatter_opts_default": (None, [C.POINTER(RtScatterOpts)]),
+    "world_scatter": (_I, [_P, _I, _I, C.POINTER(RtScatterOpts), C.POINTER(RtRay), C.POINTER(C.c_double),
+                           C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(RtScatter)]),
+    "world_scatter_device": (_I, [_P, _I, _I, C.POINTER(RtScatterOpts), _P, _P, _P, C.c_uint64, _P]),
     "shard_rows": (_U, [C.POINTER(RtCamera), C.POINTER(RtRenderOpts)]),
     "render_device": (_I, [_P, _I, _I, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), _P]),
     "render_device_wait": (_I, [_P, C.POINTER(RtStats)]),
@@ -248,7 +288,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "lights_opts_default", "lights_pdf", "lights_pdf_device", "lights_sample", "lights_sample_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "lights_opts_default", "lights_pdf", "lights_pdf_device", "lights_sample", "lights_sample_device", "scatter_opts_default", "world_scatter", "world_scatter_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

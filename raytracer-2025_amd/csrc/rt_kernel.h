@@ -1,7 +1,7 @@
 // rt_kernel.h -- interface between the host render driver (rt_render.cpp) and
 // the gfx950 kernels (rt_kernel_path.hip, rt_kernel_hit.hip,
 // rt_kernel_occl.hip, rt_kernel_radiance.hip, rt_kernel_lights.hip,
-// rt_kernel_common.hip).
+// rt_kernel_scatter.hip, rt_kernel_common.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -196,6 +196,17 @@ extern "C" __attribute__((weak)) hipError_t rtk_launch_lights_sample(const rtk::
                                                                      struct rt_light_sample* out, uint64_t n,
                                                                      uint64_t seed, uint32_t first_index, uint32_t samples,
                                                                      int grid, hipStream_t stream);
+// rt_world_scatter's kernel: one ray_color level (emitted, scatter, the PDF's
+// generate / value) of each of n rays, one rt_scatter a ray (device arrays;
+// eval_dirs3 and indices may be NULL; out 16-B aligned).  The Rng of ray i is
+// (seed, indices ? indices[i] : first_index + i, sample, vertex).  All six
+// tiers; grid and weakness as rtk_launch_hits.
+struct rt_scatter;
+extern "C" __attribute__((weak)) hipError_t rtk_launch_scatter(const rtk::SceneView* view, const struct rt_ray* rays,
+                                                               const double* eval_dirs3, const uint32_t* indices,
+                                                               struct rt_scatter* out, uint64_t n, uint64_t seed,
+                                                               uint32_t first_index, uint32_t sample, uint32_t vertex,
+                                                               int tier, int grid, void* stack_ovf, hipStream_t stream);
 // The Disney self-test (rt_disney_selftest): fn's doubles per case in and out
 // (0 for an unknown fn), and n cases of the BSDF's device functions as the
 // path kernel's Disney tier compiles them.  Weak as rtk_launch_hits is: absent

@@ -28,14 +28,16 @@
 //   rt_walk4.h    the 4-wide node visits, trace4_step (basic tier)
 //   rt_record.h   make_record;  rt_lights.h  the lights' pdf_value / random
 //   rt_shade.h    shade, shade_hit_basic
+//   rt_scatter.h  scatter_level: one level handed back (the scatter unit only)
 // beside the headers the CPU tests compile too (rt_slab.h, rt_sort4.h, ...).
 //
 // This file is the whole build (the check library, whose kernels share one
-// g_check, and the A/B libraries): the six units.  The product library
+// g_check, and the A/B libraries): the seven units.  The product library
 // compiles each as an object of its own, the path kernel's once per tier.
 #include "rt_kernel_path.hip"
 #include "rt_kernel_hit.hip"
 #include "rt_kernel_occl.hip"
 #include "rt_kernel_radiance.hip"
 #include "rt_kernel_lights.hip"
+#include "rt_kernel_scatter.hip"
 #include "rt_kernel_common.hip"

@@ -379,9 +379,11 @@ struct FlatWorld {
     size_t n_prims = 0;
     // for_query: the world of a hit / occlusion query.  Materials do not reach
     // those kernels, so a Disney or Portal world takes the tier, and with it
-    // the node format, it would take without F_DISNEY and F_PORTAL
+    // the node format, it would take without F_DISNEY and F_PORTAL -- and
+    // without F_GENERAL, which a query's world (lights = -1) has from nested
+    // wrapper materials only: the hit and occlusion kernels have no general tier
     bool for_query = false;
-    bool has_disney = false;  // ... or a Portal
+    bool has_disney = false;  // ... or a Portal, or nested wrappers
 };
 
 static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg, bool reference_bvh, FlatWorld& fw) {
@@ -394,8 +396,9 @@ static int32_t build_flat(rt_scene* s, int32_t world, int32_t lights, int32_t bg
     auto t0 = std::chrono::steady_clock::now();
     HostWorld hw;
     int32_t rc = flatten(s, world, lights, bg, reference_bvh, hw);
-    fw.has_disney = rc == RT_OK && (hw.features & (rtk::F_DISNEY | rtk::F_PORTAL)) != 0;
-    if (fw.for_query) hw.features &= ~(rtk::F_DISNEY | rtk::F_PORTAL);
+    constexpr uint32_t MATERIAL_TIERS = rtk::F_DISNEY | rtk::F_PORTAL | rtk::F_GENERAL;
+    fw.has_disney = rc == RT_OK && (hw.features & MATERIAL_TIERS) != 0;
+    if (fw.for_query) hw.features &= ~MATERIAL_TIERS;  // (for_query: lights = -1, so F_GENERAL is the materials')
     int tier = rc == RT_OK ? prepare_tier(hw) : -1;
     if (rc == RT_OK && tier < 0) rc = RT_ESTACK;
 #ifdef RT_CHECK
@@ -1372,6 +1375,132 @@ int32_t rt_world_radiance(rt_scene* s, int32_t world, int32_t lights, const rt_r
     } else {
         try {
             rc = radiance_enqueue(s, world, lights, opts, (const rt_ray*)buf, n, out_dev, nullptr);
+        } catch (const std::bad_alloc&) {
+            rc = set_error(RT_ENOMEM, "out of host memory");
+        }
+        if (rc == RT_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) rc = hip_fail(e, "query (stream synchronize)");
+        if (rc == RT_OK && (e = hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = hip_fail(e, "hipMemcpy results");
+        if (rc == RT_OK && rtk_check_read) {  // check build: refs past their arrays, as a render reports them
+            unsigned long long c[2] = {0, 0};
+            if ((e = (hipError_t)rtk_check_read(c, 1)) != hipSuccess)
+                rc = hip_fail(e, "check counters");
+            else if (c[0])
+                rc = set_error(RT_EPANIC, "check build: " + std::to_string(c[0]) +
+                                              " decoded ref(s) past their array (first: kind " +
+                                              std::to_string(rtk::ref_kind((uint32_t)c[1])) + ", index " +
+                                              std::to_string(rtk::ref_index((uint32_t)c[1])) + ")");
+        }
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+// ---- rt_world_scatter: one ray_color level (emitted, scatter, the PDF) for caller-given rays
+void rt_scatter_opts_default(rt_scatter_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof *o);
+    o->struct_size = (uint32_t)sizeof *o;
+    o->vertex = 1;
+    o->background_tex = -1;
+}
+
+static int32_t check_triples(const double* a, uint64_t n, bool nonzero, const char* what);  // (the lights queries', below)
+
+// The argument checks of both variants; n == 0 is decided by the caller after them
+static int32_t scatter_args(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* o, const void* rays,
+                            const void* indices, uint64_t n, const void* out) {
+    if (!s) return set_error(RT_EINVAL, "null scene");
+    if (!o) return set_error(RT_EINVAL, "null options");
+    if (o->struct_size < sizeof(rt_scatter_opts))  // this version reads every field below
+        return set_error(RT_EINVAL, "rt_scatter_opts.struct_size is " + std::to_string(o->struct_size) +
+                                        ", this version needs " + std::to_string(sizeof(rt_scatter_opts)) +
+                                        ": initialise the options with rt_scatter_opts_default");
+    if (o->flags & ~RT_FLAG_REFERENCE_BVH) return set_error(RT_EINVAL, "unknown flags");
+    // (the main stream's Philox counter holds vertex * 8 + slot / 2 in 32 bits: rng_contract.hpp)
+    if (o->vertex < 1 || o->vertex >= (1u << 28)) return set_error(RT_EINVAL, "vertex must be in [1, 2^28)");
+    if (n >= (1ull << 32)) return set_error(RT_EINVAL, "n must be below 2^32");
+    if (!indices && n > (1ull << 32) - o->first_index)
+        return set_error(RT_EINVAL, "first_index + n must not pass 2^32 (a ray's index is its RNG pixel)");
+    const int32_t rc = validate_handles(s, world, lights, o->background_tex);
+    if (rc != RT_OK) return rc;
+    if (n && (!rays || !out)) return set_error(RT_EINVAL, "null ray or output array");
+    return RT_OK;
+}
+
+// Enqueues the query on `stream` of the current device: the world cache and
+// the ordering are rt_world_radiance's (radiance_enqueue)
+static int32_t scatter_enqueue(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* o,
+                               const rt_ray* rays_dev, const double* eval_dev, const uint32_t* indices_dev, uint64_t n,
+                               rt_scatter* out_dev, hipStream_t stream) {
+    int cur = -1;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice (no HIP device)");
+    if (!rtk_launch_scatter) return set_error(RT_EUNSUPPORTED, "this build holds no scatter-query kernels");
+    DeviceWorld* d = nullptr;
+    int32_t rc = query_slot(s, d);
+    if (rc != RT_OK) return rc;
+    FlatWorld fw;
+    double flatten_ms = 0;
+    if ((rc = upload_world(s, d, world, lights, o->background_tex, (o->flags & RT_FLAG_REFERENCE_BVH) != 0, fw,
+                           flatten_ms)) != RT_OK)
+        return rc;
+    if ((rc = query_order(s->rs, d, stream)) != RT_OK) return rc;
+    // RT_SCATTER_GRID caps the grid (a measurement and test knob, like
+    // RT_LIGHTS_GRID): with fewer lanes than rays every lane makes several
+    // grid-stride trips, which a small batch otherwise never does
+    const uint32_t grid = std::max(1u, std::min((uint32_t)d->grid[d->tier], env_u32("RT_SCATTER_GRID", ~0u)));
+    e = rtk_launch_scatter(&d->view, rays_dev, eval_dev, indices_dev, out_dev, n, o->seed, o->first_index, o->sample,
+                           o->vertex, d->tier, (int)grid, d->stack_ovf, stream);
+    if (e != hipSuccess) return hip_fail(e, "scatter kernel launch");
+    if ((e = hipEventRecord(d->ev_done, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    d->done_recorded = true;
+    return RT_OK;
+}
+
+int32_t rt_world_scatter_device(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* opts,
+                                const rt_ray* rays_dev, const double* eval_dev, const uint32_t* indices_dev, uint64_t n,
+                                rt_scatter* out_dev) {
+    const int32_t rc = scatter_args(s, world, lights, opts, rays_dev, indices_dev, n, out_dev);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((uintptr_t)out_dev & 15u) return set_error(RT_EINVAL, "out_device must be 16-B aligned");
+    try {
+        return scatter_enqueue(s, world, lights, opts, rays_dev, eval_dev, indices_dev, n, out_dev,
+                               (hipStream_t)opts->stream);
+    } catch (const std::bad_alloc&) {
+        return set_error(RT_ENOMEM, "out of host memory");
+    }
+}
+
+// The host variant: one allocation for the records, the rays, the eval
+// directions and the indices (in that order: each part 16-B aligned or better
+// needs no padding but the last), copied in, queried on the default stream,
+// copied out
+int32_t rt_world_scatter(rt_scene* s, int32_t world, int32_t lights, const rt_scatter_opts* opts, const rt_ray* rays,
+                         const double* eval_dirs3, const uint32_t* indices, uint64_t n, rt_scatter* out) {
+    int32_t rc = scatter_args(s, world, lights, opts, rays, indices, n, out);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = check_rays(rays, n)) != RT_OK) return rc;
+    if (eval_dirs3 && (rc = check_triples(eval_dirs3, n, true, "eval direction")) != RT_OK) return rc;
+    char* buf = nullptr;
+    const size_t out_bytes = (size_t)n * sizeof(rt_scatter), ray_bytes = (size_t)n * sizeof(rt_ray);
+    const size_t eval_bytes = eval_dirs3 ? (size_t)n * 3 * sizeof(double) : 0;
+    const size_t idx_bytes = indices ? (size_t)n * sizeof(uint32_t) : 0;
+    hipError_t e = hipMalloc((void**)&buf, out_bytes + ray_bytes + eval_bytes + idx_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc scatter query");
+    rt_scatter* out_dev = (rt_scatter*)buf;  // (hipMalloc's alignment: 256 B)
+    char* rays_dev = buf + out_bytes;
+    char* eval_dev = rays_dev + ray_bytes;
+    char* idx_dev = eval_dev + eval_bytes;
+    if ((e = hipMemcpy(rays_dev, rays, ray_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (eval_dirs3 && (e = hipMemcpy(eval_dev, eval_dirs3, eval_bytes, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (indices && (e = hipMemcpy(idx_dev, indices, idx_bytes, hipMemcpyHostToDevice)) != hipSuccess)) {
+        rc = hip_fail(e, "hipMemcpy scatter query");
+    } else {
+        try {
+            rc = scatter_enqueue(s, world, lights, opts, (const rt_ray*)rays_dev,
+                                 eval_dirs3 ? (const double*)eval_dev : nullptr,
+                                 indices ? (const uint32_t*)idx_dev : nullptr, n, out_dev, nullptr);
         } catch (const std::bad_alloc&) {
             rc = set_error(RT_ENOMEM, "out of host memory");
         }

@@ -21,7 +21,7 @@ import os
 import numpy as np
 
 from .capi import (Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtLightSample, RtLightsOpts, RtRadiance,
-                   RtRadianceOpts, RtRay, RtRenderOpts, RtStats, d3, d4)
+                   RtRadianceOpts, RtRay, RtRenderOpts, RtScatter, RtScatterOpts, RtStats, d3, d4)
 
 # rt_hit_record as a numpy record (80 B, the C layout)
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
@@ -33,6 +33,11 @@ assert RADIANCE_DTYPE.itemsize == C.sizeof(RtRadiance)
 # rt_light_sample as a numpy record (40 B, the C layout)
 LIGHT_SAMPLE_DTYPE = np.dtype([("dir", "<f8", (3,)), ("pdf", "<f8"), ("flags", "<u4"), ("reserved", "<u4")])
 assert LIGHT_SAMPLE_DTYPE.itemsize == C.sizeof(RtLightSample)
+# rt_scatter as a numpy record (224 B, the C layout)
+SCATTER_DTYPE = np.dtype([("hit", HIT_DTYPE), ("emitted", "<f8", (3,)), ("f", "<f8", (3,)), ("pdf", "<f8"),
+                          ("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("eval_f", "<f8", (3,)), ("eval_pdf", "<f8"),
+                          ("flags", "<u4"), ("draws", "<u4")])
+assert SCATTER_DTYPE.itemsize == C.sizeof(RtScatter)
 
 
 class Texture:
@@ -315,6 +320,62 @@ class Scene:
         o = self._radiance_opts(max_depth, samples, seed, background, first_index, flags, stream)
         self._c(self.api.world_radiance_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
                                                C.c_void_p(int(rays_ptr)), int(n), C.c_void_p(int(out_ptr))))
+
+    # ---- one ray_color level: Material::emitted / ::scatter and the PDF (camera.rs:286-316)
+    def _scatter_opts(self, seed, sample, vertex, first_index, background, flags, stream=None):
+        o = RtScatterOpts()
+        self.api.scatter_opts_default(C.byref(o))
+        o.seed, o.sample, o.vertex, o.first_index, o.flags = int(seed), int(sample), int(vertex), int(first_index), int(flags)
+        o.background_tex = -1 if background is None else background.h
+        o.stream = C.c_void_p(stream) if stream else None
+        return o
+
+    def scatter(self, world, lights, rays, *, eval_dirs=None, indices=None, seed=0, sample=0, vertex=1, first_index=0,
+                background=None, flags=0):
+        """One ray_color level for each row of the (n, 8) float64 array `rays`,
+        as `hit` takes them (rt_world_scatter): the hit record, what the
+        surface emits, and Material::scatter -- a ray with its attenuation, or
+        a PDF's generate() with its value -- without the lights mix.
+        `eval_dirs` ((n, 3) float64 or None): directions whose PDF::value is
+        returned too (eval_f, eval_pdf).  `indices` ((n,) uint32 or None): the
+        RNG pixel of each ray, first_index + i when None; `sample` and `vertex`
+        are the key's other coordinates.  `lights` only names the flattening.
+        Returns n records as a numpy structured array (SCATTER_DTYPE)."""
+        a = np.ascontiguousarray(rays, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) array: origin, direction, time, t_max")
+        n = a.shape[0]
+        e = i = None
+        if eval_dirs is not None:
+            e = self._triples(eval_dirs, "eval_dirs")
+            if e.shape[0] != n:
+                raise ValueError("eval_dirs must have one row a ray")
+        if indices is not None:
+            i = np.ascontiguousarray(indices, dtype=np.uint32)
+            if i.shape != (n,):
+                raise ValueError("indices must be an (n,) array")
+        out = np.zeros(n, dtype=SCATTER_DTYPE)
+        o = self._scatter_opts(seed, sample, vertex, first_index, background, flags)
+        self._c(self.api.world_scatter(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                       a.ctypes.data_as(C.POINTER(RtRay)),
+                                       e.ctypes.data_as(C.POINTER(C.c_double)) if e is not None else None,
+                                       i.ctypes.data_as(C.POINTER(C.c_uint32)) if i is not None else None, n,
+                                       out.ctypes.data_as(C.POINTER(RtScatter))))
+        return out
+
+    def scatter_device(self, world, lights, rays_ptr, n, out_ptr, *, eval_dirs_ptr=None, indices_ptr=None, seed=0,
+                       sample=0, vertex=1, first_index=0, background=None, flags=0, stream=None):
+        """rt_world_scatter_device: n rt_ray at the device address rays_ptr, n
+        rt_scatter (SCATTER_DTYPE) written at the 16-B aligned out_ptr;
+        eval_dirs_ptr (n packed triples of doubles) and indices_ptr (n uint32)
+        are device addresses or None.  Enqueued on `stream` (a hipStream_t as
+        an integer; None = the default stream) without waiting."""
+        o = self._scatter_opts(seed, sample, vertex, first_index, background, flags, stream)
+        self._c(self.api.world_scatter_device(self.s, world.h, -1 if lights is None else lights.h, C.byref(o),
+                                              C.c_void_p(int(rays_ptr)),
+                                              C.c_void_p(int(eval_dirs_ptr)) if eval_dirs_ptr else None,
+                                              C.c_void_p(int(indices_ptr)) if indices_ptr else None, int(n),
+                                              C.c_void_p(int(out_ptr))))
 
     # ---- Hittable::pdf_value / ::random of the lights (hit.rs:46-60, pdf.rs:66-88)
     def _lights_opts(self, samples=1, seed=0, first_index=0, background=None, flags=0, stream=None):
