@@ -165,8 +165,32 @@ int32_t rt_constant_medium_new(rt_scene* s, int32_t boundary, double density, in
  * vanilla != 0: Metal / Dielectric from Pm / Tf (obj.rs:289-298); image maps
  * (map_Kd, map_Ke, map_d, map_Bump / normal) are decoded as rt_tex_image_file
  * does (obj.rs:212-345: map_d -> Mix::from_image(Transparent, mat)); Disney
- * materials -> RT_EUNSUPPORTED.  Returns a Hittables object (possibly empty). */
+ * materials -> RT_EUNSUPPORTED.  Returns a Hittables object (possibly empty).
+ * rt_wavefront_load_flags(.., RT_OBJ_DISNEY) builds the Disney materials. */
 int32_t rt_wavefront_load(rt_scene* s, const char* obj_path, int32_t vanilla);
+/* Wavefont::new in full.  flags:
+ *   RT_OBJ_VANILLA  Wavefont::new's vanilla_material: Metal where Pm == 1,
+ *                   Dielectric where the mean of Tf == 1 (obj.rs:271-278)
+ *   RT_OBJ_DISNEY   every other material is the Disney of obj.rs:279-292:
+ *                   rt_mat_disney(base, params), base the texture the other
+ *                   arms use (map_Kd, else Kd), params rt_disney_params_default
+ *                   with roughness = Pr (0.5 when absent), anisotropic = aniso
+ *                   (0), sheen = Ps (0), metallic = Pm (0), clearcoat = Pc (0),
+ *                   clearcoat_gloss = Pcr (0), ior = Ni (1.45), spec_trans =
+ *                   the mean of Tf's numbers (0); a value that does not parse
+ *                   as str::parse::<f64> takes the default.  Ke, map_Ke, map_d,
+ *                   d and the normal map wrap it as they wrap the other arms.
+ * Without RT_OBJ_DISNEY such a material is refused as rt_wavefront_load
+ * refuses it (callers of ABI 3 rely on that): rt_wavefront_load(s, p, vanilla)
+ * is rt_wavefront_load_flags(s, p, vanilla ? RT_OBJ_VANILLA : 0).
+ * A Disney parameter that comes out non-finite (`Tf` without a number is
+ * 0 / 0, `Pr nan`) makes the reference render NaNs and rt_mat_disney refuses
+ * it: the load is RT_EUNSUPPORTED, and rt_last_error names the material and
+ * the MTL key.  Unknown flag bits: RT_EINVAL.  Everything else (paths, missing
+ * files, panics, ownership) as rt_wavefront_load. */
+#define RT_OBJ_VANILLA 1u /* Wavefont::new's vanilla_material */
+#define RT_OBJ_DISNEY 2u  /* build obj.rs:279-292's Disney where rt_wavefront_load refuses */
+int32_t rt_wavefront_load_flags(rt_scene* s, const char* obj_path, uint32_t flags);
 
 /* Quaternion::from_axis_angle / from_euler (utils/quaternion.rs:23-53), host helpers */
 int32_t rt_quat_from_axis_angle(const double axis[3], double angle_degrees, double out_wxyz[4]);

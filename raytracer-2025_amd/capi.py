@@ -198,6 +198,8 @@ class RtScatter(C.Structure):
 
 
 SCATTER_RAY, SCATTER_PDF, SCATTER_NO_SAMPLE, SCATTER_EVAL, SCATTER_PANIC = 1, 2, 4, 8, 16
+# rt_wavefront_load_flags
+OBJ_VANILLA, OBJ_DISNEY = 1, 2
 
 _P = C.c_void_p
 _I = C.c_int32
@@ -240,6 +242,7 @@ SIGNATURES = {
     "transform_new": (_I, [_P, _I, _DP, _DP, _DP]),
     "constant_medium_new": (_I, [_P, _I, _D, _I]),
     "wavefront_load": (_I, [_P, C.c_char_p, _I]),
+    "wavefront_load_flags": (_I, [_P, C.c_char_p, _U]),
     "quat_from_axis_angle": (_I, [_DP, _D, _DP]),
     "quat_from_euler": (None, [_D, _D, _D, _DP]),
     "camera_default": (None, [C.POINTER(RtCamera)]),
@@ -288,7 +291,7 @@ SIGNATURES = {
 
 # Entry points of the product library only (the oracle renders on host cores
 # and has no communicator, device-side partial sums or parallel builders).
-GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "lights_opts_default", "lights_pdf", "lights_pdf_device", "lights_sample", "lights_sample_device", "scatter_opts_default", "world_scatter", "world_scatter_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
+GPU_ONLY = ("world_hit", "world_hit_device", "world_occluded", "world_occluded_device", "radiance_opts_default", "world_radiance", "world_radiance_device", "lights_opts_default", "lights_pdf", "lights_pdf_device", "lights_sample", "lights_sample_device", "scatter_opts_default", "world_scatter", "world_scatter_device", "render_gather_mode", "render_partials_get", "render_primary_get", "math_selftest", "walk_selftest", "disney_params_default", "mat_disney", "mat_portal", "wavefront_load_flags", "disney_selftest", "bvh_selftest", "world_selftest", "comm_unique_id", "comm_init", "comm_destroy")
 
 # Entry points only a CPU implementation has (the oracle).
 ORACLE_EXTRAS = {

@@ -1,5 +1,5 @@
 // rt_obj.cpp -- Wavefont::new (src/shapes/obj.rs:117-134) for the C ABI:
-// rt_wavefront_load.
+// rt_wavefront_load and rt_wavefront_load_flags.
 //
 // OBJ/MTL parsing restates what the reference gets from tobj 4.0.3 with
 // GPU_LOAD_OPTIONS (obj.rs:93, 104): single_index (one vertex per distinct
@@ -19,6 +19,7 @@
 //    (u, v) become texture coordinates.
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <iterator>
@@ -184,9 +185,9 @@ int64_t parse_index(const char* b, const char* e) {
     return v;
 }
 
-}  // namespace
-
-extern "C" int32_t rt_wavefront_load(rt_scene* s, const char* obj_path, int32_t vanilla) {
+// Wavefont::new; `disney`: the third arm of obj.rs:271-293 is built (rt_wavefront_load_flags
+// with RT_OBJ_DISNEY), else refused as rt_wavefront_load has always refused it
+int32_t wavefront_load(rt_scene* s, const char* obj_path, bool vanilla, bool disney) {
     if (!s || !obj_path) return set_error(RT_EINVAL, "null argument");
     try {
         std::ifstream f(obj_path, std::ios::binary);
@@ -336,8 +337,32 @@ extern "C" int32_t rt_wavefront_load(rt_scene* s, const char* obj_path, int32_t 
                 mat = rt_mat_metal(s, albedo, roughness);
             } else if (vanilla && spec_trans == 1.0) {
                 mat = rt_mat_dielectric(s, base_tex, ior);
-            } else {
+            } else if (!disney) {
                 return set_error(RT_EUNSUPPORTED, "Disney BSDF materials (obj.rs:299-311) are not on the kernel path");
+            } else {
+                // Disney { param_fn: |u, v, p| DisneyParameters { base_color: base_color.value(u, v, p),
+                // roughness, anisotropic, sheen, clearcoat, clearcoat_gloss, metallic, ior, spec_trans,
+                // ..Default::default() } } (obj.rs:279-292)
+                rt_disney_params dp;
+                rt_disney_params_default(&dp);
+                dp.roughness = roughness;
+                dp.anisotropic = param_or(m, "aniso", 0.0);
+                dp.sheen = param_or(m, "Ps", 0.0);
+                dp.clearcoat = param_or(m, "Pc", 0.0);
+                dp.clearcoat_gloss = param_or(m, "Pcr", 0.0);
+                dp.metallic = metallic;
+                dp.ior = ior;
+                dp.spec_trans = spec_trans;
+                // a non-finite one renders NaNs in the reference; rt_mat_disney takes none
+                const std::pair<const char*, double> keys[] = {
+                    {"Pr", dp.roughness}, {"aniso", dp.anisotropic},   {"Ps", dp.sheen}, {"Pm", dp.metallic},
+                    {"Pc", dp.clearcoat}, {"Pcr", dp.clearcoat_gloss}, {"Ni", dp.ior},   {"Tf", dp.spec_trans}};
+                for (const auto& k : keys)
+                    if (!std::isfinite(k.second))
+                        return set_error(RT_EUNSUPPORTED, "material '" + m.name + "': the Disney parameter of `" + k.first +
+                                                              "` is not finite (the reference renders NaNs)");
+                mat = rt_mat_disney(s, base_tex, &dp);
+                if (mat < 0) return mat;
             }
             std::vector<double> ke = params(m, "Ke");
             if (ke.size() == 3) mat = rt_mat_diffuse_light(s, rt_tex_solid(s, ke.data()), mat);
@@ -443,4 +468,15 @@ extern "C" int32_t rt_wavefront_load(rt_scene* s, const char* obj_path, int32_t 
     } catch (const std::exception& e) {
         return set_error(RT_EINVAL, std::string("OBJ parse error: ") + e.what());
     }
+}
+
+}  // namespace
+
+extern "C" int32_t rt_wavefront_load(rt_scene* s, const char* obj_path, int32_t vanilla) {
+    return wavefront_load(s, obj_path, vanilla != 0, false);
+}
+
+extern "C" int32_t rt_wavefront_load_flags(rt_scene* s, const char* obj_path, uint32_t flags) {
+    if (flags & ~(RT_OBJ_VANILLA | RT_OBJ_DISNEY)) return set_error(RT_EINVAL, "unknown rt_wavefront_load_flags flags");
+    return wavefront_load(s, obj_path, (flags & RT_OBJ_VANILLA) != 0, (flags & RT_OBJ_DISNEY) != 0);
 }

@@ -20,8 +20,9 @@ import os
 
 import numpy as np
 
-from .capi import (Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtLightSample, RtLightsOpts, RtRadiance,
-                   RtRadianceOpts, RtRay, RtRenderOpts, RtScatter, RtScatterOpts, RtStats, d3, d4)
+from .capi import (OBJ_DISNEY, OBJ_VANILLA, Api, RtCamera, RtDisneyParams, RtError, RtHitRecord, RtLightSample,
+                   RtLightsOpts, RtRadiance, RtRadianceOpts, RtRay, RtRenderOpts, RtScatter, RtScatterOpts, RtStats, d3,
+                   d4)
 
 # rt_hit_record as a numpy record (80 B, the C layout)
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
@@ -229,13 +230,20 @@ class Scene:
     def ConstantMedium(self, boundary, density, tex):
         return Hittable(self, self._c(self.api.constant_medium_new(self.s, boundary.h, float(density), tex.h)), "medium")
 
-    def Wavefont(self, obj_path, vanilla_material=True):
+    def Wavefont(self, obj_path, vanilla_material=True, disney=False):
         """Wavefont::new (shapes/obj.rs:117-134); returns the Hittables of its
         per-model BVHs.  The reference's Option<Wavefont> is None when the OBJ
-        cannot be opened: here that raises RtError(RT_EINVAL)."""
-        rc = self.api.wavefront_load(self.s, os.fsencode(obj_path), 1 if vanilla_material else 0)
+        cannot be opened: here that raises RtError(RT_EINVAL).  disney=True is
+        Wavefont::new in full (rt_wavefront_load_flags with RT_OBJ_DISNEY):
+        every material that is no vanilla Metal / Dielectric becomes the Disney
+        of obj.rs:279-292; with disney=False the old entry point is called and
+        refuses such a material (RT_EUNSUPPORTED)."""
+        path = os.fsencode(obj_path)
+        if disney:
+            rc = self.api.wavefront_load_flags(self.s, path, OBJ_DISNEY | (OBJ_VANILLA if vanilla_material else 0))
+        else:
+            rc = self.api.wavefront_load(self.s, path, 1 if vanilla_material else 0)
         return Hittables(self, self._c(rc), "list")
-
 
     # ---- Hittable::hit (hit.rs:46-60)
     def hit(self, world, rays, seed=0, flags=0):
@@ -462,10 +470,22 @@ class Camera:
     @staticmethod
     def from_json(api, path):
         """Camera::from_json (camera.rs:119-159): the CameraParams fields from a
-        JSON file over Camera::default (path given directly)."""
+        JSON file over Camera::default (path given directly).  An
+        implementation without rt_camera_from_json (a CPU one: file I/O is the
+        product library's) gets the same fields through Python's json."""
+        cam = Camera()
+        if not hasattr(api, "camera_from_json"):
+            import json
+            with open(path, encoding="utf-8") as f:
+                params = json.load(f)
+            for name in ("aspect_ratio", "vertical_fov_in_degrees", "defocus_angle_in_degrees", "focus_distance"):
+                setattr(cam, name, float(params[name]))
+            cam.image_width = int(params["image_width"])
+            for name in ("look_from", "look_at", "vec_up"):
+                setattr(cam, name, tuple(float(x) for x in params[name]))
+            return cam
         c = RtCamera()
         api.check(api.camera_from_json(os.fsencode(path), C.byref(c)))
-        cam = Camera()
         cam.aspect_ratio = c.aspect_ratio
         cam.image_width = c.image_width
         cam.vertical_fov_in_degrees = c.vertical_fov_in_degrees

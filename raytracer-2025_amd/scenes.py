@@ -284,3 +284,167 @@ def portal_scene(scene, background=None, image_width=1920, samples_per_pixel=500
     cam.toon_map = 1  # ToonMap::ACES
     cam.background = background if background is not None else scene.SkyGradient((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))
     return world, None, cam
+
+
+def _sky(scene, background):
+    return background if background is not None else scene.SkyGradient((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))
+
+
+def disney_scene(scene, background=None, image_width=1920, samples_per_pixel=500, max_depth=10):
+    """src/main.rs:92-153 disney_scene(): one unit sphere at the origin under
+    Disney::builder() with base_color WHITE, roughness 0, metallic 1, ior 1.5
+    and every other field spelled out at its default (main.rs:95-112), 16:9,
+    ACES tone map, `camera.render(&world, None)`.
+
+    The reference lights it with rogland_clear_night_4k.exr (main.rs:149-150),
+    which no decoder here reads: the background is a parameter, as in
+    portal_scene."""
+    disney = scene.Disney(scene.SolidColor((1.0, 1.0, 1.0)), roughness=0.0, anisotropic=0.0, sheen=0.0, sheen_tint=0.0,
+                          clearcoat=0.0, clearcoat_gloss=0.0, specular_tint=0.0, metallic=1.0, ior=1.5, flatness=0.0,
+                          spec_trans=0.0, diff_trans=0.0, thin=False)  # main.rs:95-112
+    world = scene.Hittables()
+    world.add(scene.Sphere((0.0, 0.0, 0.0), 1.0, disney))  # main.rs:124
+    cam = Camera()
+    cam.aspect_ratio = 16.0 / 9.0  # main.rs:136-139
+    cam.image_width = image_width
+    cam.samples_per_pixel = samples_per_pixel
+    cam.max_depth = max_depth
+    cam.vertical_fov_in_degrees = 40.0  # main.rs:141-144
+    cam.look_from = (-4.0, 2.0, 0.0)  # Point3::new(-2.0, 1.0, 0.0) * 2.0, exact
+    cam.look_at = (0.0, 0.0, 0.0)
+    cam.vec_up = (0.0, 1.0, 0.0)
+    cam.defocus_angle_in_degrees = 0.0  # main.rs:146-147
+    cam.toon_map = 1  # ToonMap::ACES
+    cam.background = _sky(scene, background)
+    return world, None, cam  # main.rs:152
+
+
+def background_scene(scene, background=None, image_width=1920, samples_per_pixel=100, max_depth=10):
+    """src/main.rs:155-205 background_scene(): a Mix(Metal, Lambertian, 0.5)
+    floor quad and a small sphere of Mix(DiffuseLight, Metal, 0.5), which is
+    also the lights (`camera.render(&world, Some(&light))`, main.rs:200): the
+    reference clones the sphere, an object here moves into its list, so the
+    sphere is built a second time with the same material.  16:9, ACES tone
+    map; the background (main.rs:197-198, the EXR) is a parameter, as in
+    portal_scene."""
+    metal_mat = scene.Metal((1.0, 1.0, 1.0), 0.0)  # main.rs:163
+    lam_mat = scene.Lambertian(scene.SolidColor((0.8, 0.8, 0.8)))  # main.rs:164-166
+    mix_mat = scene.Mix(metal_mat, lam_mat, 0.5)  # main.rs:167
+    world = scene.Hittables()
+    world.add(scene.Quad((-2.0, -2.0, -2.0), (4.0, 0.0, 0.0), (0.0, 0.0, 4.0), mix_mat))  # main.rs:168-173
+    light_mat = scene.DiffuseLight(scene.SolidColor((0.75 * 1.0, 1.0 * 1.0, 0.58 * 1.0)))  # main.rs:175-177
+    mix_mat2 = scene.Mix(light_mat, metal_mat, 0.5)  # main.rs:178
+    world.add(scene.Sphere((1.5, -1.5, 0.0), 0.2, mix_mat2))  # main.rs:179-180
+    cam = Camera()
+    cam.aspect_ratio = 16.0 / 9.0  # main.rs:184-187
+    cam.image_width = image_width
+    cam.samples_per_pixel = samples_per_pixel
+    cam.max_depth = max_depth
+    cam.vertical_fov_in_degrees = 40.0  # main.rs:189-192
+    cam.look_from = (-4.0, 2.0, 0.0)  # Point3::new(-2.0, 1.0, 0.0) * 2.0, exact
+    cam.look_at = (0.0, 0.0, 0.0)
+    cam.vec_up = (0.0, 1.0, 0.0)
+    cam.defocus_angle_in_degrees = 0.0  # main.rs:194-195
+    cam.toon_map = 1  # ToonMap::ACES
+    cam.background = _sky(scene, background)
+    lights = scene.Sphere((1.5, -1.5, 0.0), 0.2, mix_mat2)  # light.clone(), main.rs:180, 200
+    return world, lights, cam
+
+
+# main.rs:208-221: (file, vanilla_material) of every Wavefont::new(file, "Final", vanilla), in the order made
+OBJ_SCENE_OBJS = (
+    ("初音未来.obj", False), ("玻璃球.obj", False), ("外框.obj", False), ("声匣.obj", False), ("镜子门.obj", False),
+    ("镜子.obj", True), ("环.obj", False), ("传送门框.obj", False), ("水下.obj", False), ("水面.obj", True),
+    ("文字.obj", False), ("mc.obj", False), ("伞.obj", False), ("卒.obj", False),
+)
+# main.rs:312-332: the world's add order; a name is an entry of OBJ_SCENE_OBJS, a "+name" one of the built objects
+_OBJ_SCENE_ORDER = ("初音未来.obj", "+light_board", "玻璃球.obj", "外框.obj", "声匣.obj", "镜子门.obj", "镜子.obj", "环.obj",
+                    "传送门框.obj", "水下.obj", "水面.obj", "文字.obj", "+translucent_board", "mc.obj", "+portal", "伞.obj",
+                    "+yellow_board", "+black_box", "+fog", "卒.obj")
+
+
+def obj_scene(scene, asset_dir, background=None, objs=OBJ_SCENE_OBJS, fog="雾.obj", image_width=None,
+              samples_per_pixel=3000, max_depth=30):
+    """src/main.rs:207-382 obj_scene(), the scene the reference's main runs:
+    the Wavefont::new(file, "Final", vanilla) meshes of `objs` from `asset_dir`
+    (every MTL material a Disney BSDF, or with vanilla a Metal / Dielectric
+    where Pm / Tf say so, obj.rs:271-293), the fog mesh as a ConstantMedium, a
+    Portal quad, a thin translucent Disney board, two light boards and a black
+    box, added in main.rs:312-332's order; the lights are the two boards as
+    EmptyMaterial quads under their Transforms; the camera is
+    asset_dir/camera.json with 3000 spp and depth 30.
+
+    `objs`: (file, vanilla) pairs, by default all fourteen of main.rs:208-221;
+    a subset keeps the world's add order.  fog=None leaves the medium out.  A
+    named file that is absent raises (the reference's unwrap panics).
+    image_width overrides camera.json's.  The reference's background is
+    13.hdr (main.rs:339-340): a parameter here, any Texture
+    (scene.ImageTexture_file reads Radiance HDR), by default the sky gradient
+    of the other scenes."""
+    api = scene.api
+    by_name = dict(objs)
+    unknown = [f for f in by_name if f not in _OBJ_SCENE_ORDER]
+    if unknown:
+        raise ValueError("not a mesh of obj_scene: %r" % unknown)
+    for f in list(by_name) + ([fog] if fog is not None else []):
+        if not os.path.exists(os.path.join(asset_dir, f)):
+            raise FileNotFoundError(os.path.join(asset_dir, f))  # Wavefont::new(..).unwrap()
+
+    def wavefont(file, vanilla):
+        return scene.Wavefont(os.path.join(asset_dir, file), vanilla, disney=True)
+
+    # main.rs:208-221, in the order made (handles number the same way on every implementation)
+    meshes = {file: wavefont(file, by_name[file]) for file, _ in OBJ_SCENE_OBJS if file in by_name}
+    built = {}
+    if fog is not None:  # main.rs:223-228
+        built["fog"] = scene.ConstantMedium(wavefont(fog, False), 0.05, scene.SolidColor((1.0, 0.936, 0.381)))
+
+    portal_material = scene.Portal((1.0, 1.0, 1.0), (0.0, -6.3, 1.1), Quaternion.identity())  # main.rs:230-234
+    portal_anchor = (-5.8035, -0.9983, -7.7198)  # main.rs:236-239
+    portal_u = (-3.8206 - portal_anchor[0], -0.9983 - portal_anchor[1], -8.3722 - portal_anchor[2])
+    portal_v = (-5.8035 - portal_anchor[0], 3.1159 - portal_anchor[1], -7.7198 - portal_anchor[2])
+    built["portal"] = scene.Quad(portal_anchor, portal_u, portal_v, portal_material)
+
+    # main.rs:241-247: Disney::builder().diff_trans(1.0).roughness(1.0).thin(true).build(): base_color is
+    # DisneyParameters::default's (0.8, 0.8, 0.8) (disney.rs:36-55)
+    translucent_material = scene.Disney(scene.SolidColor((0.8, 0.8, 0.8)), diff_trans=1.0, roughness=1.0, thin=True)
+
+    def board(material):  # main.rs:248-253, 267-272, 285-290, 342-347, 357-362
+        return scene.Quad((-1.0, 0.0, -1.0), (0.0, 0.0, 2.0), (2.0, 0.0, 0.0), material)
+
+    def light_transform(obj):  # main.rs:273-281, 348-356
+        return scene.Transform(obj, (-0.44579, 5.2955, 0.89889),
+                               Quaternion.from_axis_angle(api, (0.921, 0.021, 0.389), 34.7), (3.415, 3.415, 3.415))
+
+    def yellow_transform(obj):  # main.rs:291-299, 363-371
+        return scene.Transform(obj, (-1.0053, -1.9655, -4.242),
+                               Quaternion.from_axis_angle(api, (0.766, 0.483, -0.423), 85.7),
+                               (1.0 * 1.499, 1.0 * 1.499, 1.0 * 1.499))
+
+    built["translucent_board"] = scene.Transform(  # main.rs:254-262
+        board(translucent_material), (2.8145, -0.23603, -19.501),
+        Quaternion.from_axis_angle(api, (0.993, -0.082, 0.082), 90.4), (2.616, 1.0, 1.0))
+    built["light_board"] = light_transform(board(scene.DiffuseLight(scene.SolidColor((4.0, 4.0, 4.0)))))  # :264-281
+    # main.rs:282-284: 5.0 * Color::new(1.0, 0.687, 0.0)
+    built["yellow_board"] = yellow_transform(board(scene.DiffuseLight(scene.SolidColor((5.0 * 1.0, 5.0 * 0.687, 5.0 * 0.0)))))
+    built["black_box"] = scene.Transform(  # main.rs:301-310
+        scene.build_box((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), scene.DiffuseLight(scene.SolidColor((0.0, 0.0, 0.0)))),
+        (-4.9891, -6.4998, -8.3939), None, (1.0 * 6.244, 1.0 * 6.244, 1.0 * 6.244))
+
+    world = scene.Hittables()  # main.rs:312-332
+    for name in _OBJ_SCENE_ORDER:
+        obj = built.get(name[1:]) if name.startswith("+") else meshes.get(name)
+        if obj is not None:
+            world.add(obj)
+
+    cam = Camera.from_json(api, os.path.join(asset_dir, "camera.json"))  # main.rs:334
+    cam.samples_per_pixel = samples_per_pixel  # main.rs:336-337
+    cam.max_depth = max_depth
+    if image_width is not None:
+        cam.image_width = image_width
+    cam.background = _sky(scene, background)  # main.rs:339-340
+
+    lights = scene.Hittables()  # main.rs:342-375
+    lights.add(light_transform(board(scene.EmptyMaterial())))
+    lights.add(yellow_transform(board(scene.EmptyMaterial())))
+    return world, lights, cam
