@@ -83,15 +83,16 @@ Perlin::Perlin(uint64_t seed) {
 }
 // perlin.rs:40-58 + 74-89
 double Perlin::noise(const Point3& p) const {
-    int64_t i = (int64_t)std::floor(p.x()), j = (int64_t)std::floor(p.y()), k = (int64_t)std::floor(p.z());
+    int64_t i = as_i64(std::floor(p.x())), j = as_i64(std::floor(p.y())), k = as_i64(std::floor(p.z()));
     double u = p.x() - std::floor(p.x()), v = p.y() - std::floor(p.y()), w = p.z() - std::floor(p.z());
     double uu = u * u * (3.0 - 2.0 * u), vv = v * v * (3.0 - 2.0 * v), ww = w * w * (3.0 - 2.0 * w);
     double accum = 0.0;
     for (int di = 0; di < 2; ++di)
         for (int dj = 0; dj < 2; ++dj)
             for (int dk = 0; dk < 2; ++dk) {
-                const Vec3& c = randvec[perm_x[(size_t)(i + di) & 255] ^ perm_y[(size_t)(j + dj) & 255] ^
-                                        perm_z[(size_t)(k + dk) & 255]];
+                // (i + di as i64) as usize & 255, the sum wrapping as in the reference's release build
+                const uint64_t xi = (uint64_t)i + (uint64_t)di, yi = (uint64_t)j + (uint64_t)dj, zi = (uint64_t)k + (uint64_t)dk;
+                const Vec3& c = randvec[perm_x[xi & 255] ^ perm_y[yi & 255] ^ perm_z[zi & 255]];
                 Vec3 weight_v(u - di, v - dj, w - dk);
                 accum += (di * uu + (1 - di) * (1.0 - uu)) * (dj * vv + (1 - dj) * (1.0 - vv)) *
                          (dk * ww + (1 - dk) * (1.0 - ww)) * c.dot(weight_v);

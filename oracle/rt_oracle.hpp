@@ -350,6 +350,30 @@ WorkCounts& work();
 #define ORC_COUNT(field) (++::orc::work().field)
 #endif
 
+// ---------------------------------------------------------------- Rust's `as` casts
+// f64 -> integer with `as` saturates at the type's bounds and takes NaN to 0;
+// a plain C++ cast is undefined out of range (on x86-64 it gives INT_MIN for
+// either sign).  The reference casts so in texture.rs:61-63, 115-116, 131-132
+// and perlin.rs:41; i32 `+` wraps in its release build.
+inline int32_t as_i32(double x) {
+    if (std::isnan(x)) return 0;
+    if (x >= 2147483648.0) return INT32_MAX;
+    if (x <= -2147483649.0) return INT32_MIN;
+    return (int32_t)x;
+}
+inline uint32_t as_u32(double x) {
+    if (std::isnan(x) || x <= -1.0) return 0;
+    if (x >= 4294967296.0) return UINT32_MAX;
+    return (uint32_t)x;
+}
+inline int64_t as_i64(double x) {
+    if (std::isnan(x)) return 0;
+    if (x >= 9223372036854775808.0) return INT64_MAX;
+    if (x < -9223372036854775808.0) return INT64_MIN;
+    return (int64_t)x;
+}
+inline int32_t wrapping_add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+
 // ---------------------------------------------------------------- Textures
 // src/texture.rs:5-7
 struct Texture {
@@ -367,10 +391,10 @@ struct CheckerTexture : Texture {  // texture.rs:39-73
     CheckerTexture(double scale, std::shared_ptr<Texture> e, std::shared_ptr<Texture> o)
         : inv_scale(1.0 / scale), even(std::move(e)), odd(std::move(o)) {}
     Color value(double u, double v, const Point3& p) const override {
-        int32_t xi = (int32_t)std::floor(inv_scale * p.x());
-        int32_t yi = (int32_t)std::floor(inv_scale * p.y());
-        int32_t zi = (int32_t)std::floor(inv_scale * p.z());
-        bool is_even = ((xi + yi + zi) % 2) == 0;
+        int32_t xi = as_i32(std::floor(inv_scale * p.x()));
+        int32_t yi = as_i32(std::floor(inv_scale * p.y()));
+        int32_t zi = as_i32(std::floor(inv_scale * p.z()));
+        bool is_even = (wrapping_add(wrapping_add(xi, yi), zi) % 2) == 0;
         return is_even ? even->value(u, v, p) : odd->value(u, v, p);
     }
 };
@@ -404,13 +428,13 @@ struct ImageTexture : Texture {
         u = abs_fract(u);
         v = 1.0 - abs_fract(v);
         if (!linear_interp) {  // texture.rs:109-118
-            uint32_t i = (uint32_t)(u * (double)w);
-            uint32_t j = (uint32_t)(v * (double)h);
+            uint32_t i = as_u32(u * (double)w);
+            uint32_t j = as_u32(v * (double)h);
             return pixel_data(i, j);
         }
         double x = u * (double)w - 0.5, y = v * (double)h - 0.5;  // texture.rs:120-153
-        uint32_t x0 = (uint32_t)std::fmax(std::floor(x), 0.0);
-        uint32_t y0 = (uint32_t)std::fmax(std::floor(y), 0.0);
+        uint32_t x0 = as_u32(std::fmax(std::floor(x), 0.0));
+        uint32_t y0 = as_u32(std::fmax(std::floor(y), 0.0));
         uint32_t x1 = std::min<uint32_t>(x0 + 1, (uint32_t)w - 1);
         uint32_t y1 = std::min<uint32_t>(y0 + 1, (uint32_t)h - 1);
         double dx = x - (double)x0, dy = y - (double)y0;

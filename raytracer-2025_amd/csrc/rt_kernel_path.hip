@@ -691,7 +691,12 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         }
         if (!end_path) {
             ++vertex;
-            if (vertex > F.max_depth) end_path = true;  // depth == 0 -> BLACK (camera.rs:282-284)
+            if (vertex > F.max_depth) {  // depth == 0 -> BLACK (camera.rs:282-284)
+                end_path = true;
+                // the recursion multiplies that BLACK by every level's f / pdf on its way up: a non-finite
+                // one (Disney's pdf = NaN at a zero weight sum) makes it NaN there (camera.rs:323)
+                if constexpr (TIER == TIER_FULL_DS) L = L + beta * d3(0, 0, 0);
+            }
         }
         if (end_path) {
             if (isnan(L.x) || isnan(L.y) || isnan(L.z)) {  // camera.rs:323

@@ -250,7 +250,11 @@ __global__ void __launch_bounds__(TIER == TIER_BASIC ? RT_BLOCK_BASIC : RT_BLOCK
         if (panic) end_path = true;
         if (!end_path) {
             ++vertex;
-            if (vertex > P.max_depth) end_path = true;  // depth == 0 -> BLACK (camera.rs:282-284)
+            if (vertex > P.max_depth) {  // depth == 0 -> BLACK (camera.rs:282-284)
+                end_path = true;
+                // as the path kernel: BLACK times a non-finite f / pdf on the recursion's way up is NaN
+                if constexpr (TIER == TIER_FULL_DS) L = L + beta * d3(0, 0, 0);
+            }
         }
         if (end_path) {
             // the sample's end: a panicked sample adds the radiance gathered

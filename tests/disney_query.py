@@ -63,13 +63,15 @@ def params_struct(api, **over):
     return p
 
 
-def selftest(api, fn, name, cases, oracle=False):
+def selftest(api, fn, name, cases, oracle=False, color=None):
     """n x 6 doubles of self-test `fn` for parameter set `name` on `api`
-    (rt_disney_selftest, or the driver's orcx_disney_selftest)."""
+    (rt_disney_selftest, or the driver's orcx_disney_selftest).  `name` is a
+    key of PARAM_SETS or a parameter dict; `color` (the base colour) defaults
+    to the named set's."""
     a = np.ascontiguousarray(cases, dtype=np.float64)
     out = np.zeros((a.shape[0], 6), dtype=np.float64)
-    p = params_struct(api, **PARAM_SETS[name])
-    base = (C.c_double * 3)(*COLORS[name])
+    p = params_struct(api, **(name if isinstance(name, dict) else PARAM_SETS[name]))
+    base = (C.c_double * 3)(*(COLORS[name] if color is None else color))
     call = api.x_disney_selftest if oracle else api.disney_selftest
     api.check(call(fn, C.byref(p), base, a.ctypes.data_as(_DP), out.ctypes.data_as(_DP), a.shape[0]))
     return out
@@ -91,14 +93,28 @@ def lobe_sums(p):
     """calculate_lobe_pdfs' running sums as generate compares them
     (disney.rs:403-422, 672-690), in its operation order: (p_specular,
     p_specular + p_clearcoat, p_specular + p_diffuse + p_clearcoat)."""
-    metallic, spec_trans = p.get("metallic", 0.0), p.get("spec_trans", 0.0)
-    specular_bsdf = (1.0 - metallic) * spec_trans
-    dielectric_brdf = (1.0 - spec_trans) * (1.0 - metallic)
-    specular_weight = metallic + dielectric_brdf
-    clearcoat_weight = 1.0 * min(max(p.get("clearcoat", 0.0), 0.0), 1.0)
-    norm = 1.0 / (specular_weight + specular_bsdf + dielectric_brdf + clearcoat_weight)
-    ps, pt, pd, pc = specular_weight * norm, specular_bsdf * norm, dielectric_brdf * norm, clearcoat_weight * norm
-    return ps, ps + pc, ps + pd + pc
+    ps, pd, pc, pt = lobe_pdfs(p)
+    with np.errstate(all="ignore"):
+        return float(ps), float(ps + pc), float(ps + pd + pc)
+
+
+def lobe_pdfs(p):
+    """calculate_lobe_pdfs (disney.rs:403-422) in IEEE doubles: (p_specular,
+    p_diffuse, p_clearcoat, p_spec_trans).  A zero weight sum gives norm = inf
+    and the products of it, as the reference computes them."""
+    f = np.float64
+    metallic, spec_trans = f(p.get("metallic", 0.0)), f(p.get("spec_trans", 0.0))
+    with np.errstate(all="ignore"):
+        specular_bsdf = (f(1.0) - metallic) * spec_trans
+        dielectric_brdf = (f(1.0) - spec_trans) * (f(1.0) - metallic)
+        specular_weight = metallic + dielectric_brdf
+        c = f(p.get("clearcoat", 0.0))
+        c = f(0.0) if c < 0.0 else c  # f64::clamp
+        c = f(1.0) if c > 1.0 else c
+        clearcoat_weight = f(1.0) * c
+        norm = f(1.0) / (specular_weight + specular_bsdf + dielectric_brdf + clearcoat_weight)
+        return (float(specular_weight * norm), float(dielectric_brdf * norm), float(clearcoat_weight * norm),
+                float(specular_bsdf * norm))
 
 
 @functools.lru_cache(maxsize=None)
@@ -143,7 +159,14 @@ def gen_cases(name):
     each lobe-boundary draw (the running sums, one ulp under and over) and
     directions within 1e-7 of the normal (the VNDF's 0.9999999 branch) and
     perpendicular to it."""
-    rng = np.random.default_rng(777 + sorted(PARAM_SETS).index(name))
+    return gen_cases_for(PARAM_SETS[name], 777 + sorted(PARAM_SETS).index(name))
+
+
+def gen_cases_for(params, seed):
+    """gen_cases for a parameter dict: the lobe-boundary draws come from its
+    own running sums; a sum that is NaN, infinite or outside [0, 1) gives no
+    boundary draw."""
+    rng = np.random.default_rng(seed)
     n = 2048
     a = np.zeros((n, 11))
     nrm = _units(rng, n)
@@ -156,11 +179,11 @@ def gen_cases(name):
     a[:, 6] = rng.integers(0, 2, n)
     a[:, 7:11] = rng.random((n, 4))
     hard = []
-    sums = lobe_sums(PARAM_SETS[name])
+    sums = lobe_sums(params)
     edges = [0.0, float(np.nextafter(1.0, 0.0))]
     for s in sums:
         edges += [s, float(np.nextafter(s, 0.0)), float(np.nextafter(s, 2.0))]
-    edges = [e for e in edges if 0.0 <= e < 1.0]
+    edges = [e for e in edges if np.isfinite(e) and 0.0 <= e < 1.0]
     base = a[:16].copy()
     for e in edges:
         for row in base[:6]:
